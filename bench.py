@@ -4,6 +4,7 @@
 
     python bench.py --gpus N --steps K --warmup W
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+    python bench.py ... --dump-outputs DIR     # also write what the timed steps computed (dump_outputs) under DIR
 
 A "step" is ONE merge iteration of ``HyperbolicTokenizer.optimize_merges`` (reference
 ``tokenizer/hyperbolic_merge.py:357-412``): a full all-pairs Lorentz-distance search for the
@@ -426,6 +427,71 @@ def tokenize_leg(device, n_lines: int = 400_000) -> dict:
             "sample_matches_cpu": all(ids[k] == w for k, w in zip(sample, want))}
 
 
+DUMP_BYTES = (64 << 20) - (64 << 10)    # 64 MB in all, less room for the .npy headers
+DUMP_SEED = 1234
+
+
+def _dump_rows(n: int, row_bytes: int, budget: int, keep_last: bool = False) -> np.ndarray | None:
+    """None when all n rows fit in `budget`, else a fixed seeded, sorted sample of row indices that does"""
+    if n * row_bytes <= budget:
+        return None
+    k = max(1, budget // row_bytes)
+    idx = np.random.RandomState(DUMP_SEED).choice(n - 1 if keep_last else n, k - 1 if keep_last else k, replace=False)
+    if keep_last:
+        idx = np.append(idx, n - 1)
+    return np.sort(idx)
+
+
+def _split_nonfinite(a: np.ndarray):
+    """`a` with every NaN / inf entry set to 0, and where they were: rows (flat index, kind 1 = NaN, 2 = +inf, 3 = -inf), f64"""
+    flat = a.reshape(-1)
+    bad = np.flatnonzero(~np.isfinite(flat))
+    kind = np.where(np.isnan(flat[bad]), 1.0, np.where(flat[bad] > 0, 2.0, 3.0))
+    clean = a.copy()
+    clean.reshape(-1)[bad] = 0
+    return clean, np.stack([bad.astype(np.float64), kind], axis=1).reshape(-1, 2)
+
+
+def dump_outputs(out_dir: str, tok, first: int) -> dict:
+    """What the timed `optimize_merges` call leaves to its caller, as .npy files for output-for-output comparison of two
+    builds: the rows its merges appended (`merged_rows`, f32, the last step's row last), each merge's left and right token
+    (`merge_tokens`, f64: index of the first vocabulary entry with that spelling) and the whole table afterwards
+    (`embeddings`, f32).  Every file holds finite numbers only: a merge of two identical rows is a NaN row (the reference's
+    arithmetic), so NaN / inf entries are written as 0 and listed in `<name>_nonfinite` (f64 rows of flat
+    index and kind).  Over 64 MB a fixed seeded sample of rows is written with its row indices (`*_rows`, f64)."""
+    os.makedirs(out_dir, exist_ok=True)
+    n = tok.current_vocab_size
+    table = tok.embeddings.data[:n].detach().float().cpu().numpy()
+    hist = tok.merge_history[first:]
+    m = len(hist)
+    first_idx = {}
+    for k, t in enumerate(tok.vocab[:n]):
+        first_idx.setdefault(t, k)
+    arrays = {"merged_rows": table[n - m:n],
+              "merge_tokens": np.array([[first_idx[a], first_idx[b]] for (a, b, _ab) in hist], dtype=np.float64).reshape(m, 2)}
+    # the lists of non-finite entries of the whole arrays bound those of any sample: reserve their room first
+    budget = DUMP_BYTES - 16 * (int((~np.isfinite(table)).sum()) + int((~np.isfinite(arrays["merged_rows"])).sum()))
+    if budget < DUMP_BYTES // 2:
+        raise SystemExit(f"--dump-outputs: {(DUMP_BYTES - budget) // 16} non-finite entries do not fit in the 64 MB of the dump")
+    row_bytes = table.shape[1] * 4 + 2 * 8
+    pick = _dump_rows(m, row_bytes, budget // 2, keep_last=True) if m else None
+    if pick is not None:
+        arrays = {k: v[pick] for k, v in arrays.items()}
+        arrays["merged_rows_rows"] = pick.astype(np.float64)
+    used = sum(v.nbytes for v in arrays.values())
+    pick = _dump_rows(n, table.shape[1] * 4 + 8, budget - used)
+    arrays["embeddings"] = table if pick is None else table[pick]
+    if pick is not None:
+        arrays["embeddings_rows"] = pick.astype(np.float64)
+    for name in ("merged_rows", "embeddings"):
+        arrays[name], arrays[f"{name}_nonfinite"] = _split_nonfinite(arrays[name])
+    for name, arr in arrays.items():
+        assert np.isfinite(arr).all(), name
+        np.save(os.path.join(out_dir, f"{name}.npy"), np.ascontiguousarray(arr))
+    return {"dir": out_dir, "files": {k: list(v.shape) for k, v in arrays.items()},
+            "bytes": int(sum(v.nbytes for v in arrays.values()))}
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -433,6 +499,8 @@ def main() -> None:
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-legs", action="store_true", help="headline line only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed steps computed as DIR/<name>.npy (rank 0; at most 64 MB)")
     args = ap.parse_args()
 
     rank = int(os.environ.get("RANK", "0"))
@@ -510,12 +578,16 @@ def main() -> None:
     if timing:
         eng.debug_time_loops(True)
     eng.scan_totals(reset=True)
+    first = len(tok.merge_history)
     barrier()
     t0 = time.perf_counter()
     tok.optimize_merges(steps=args.steps, log_every=10 ** 9)
     barrier()
     elapsed = time.perf_counter() - t0
-    merges_done = len(tok.merge_history) - args.warmup
+    merges_done = len(tok.merge_history) - first
+    if merges_done != args.steps:
+        raise SystemExit(f"the timed run merged {merges_done} pairs, not --steps {args.steps}: out of candidates")
+    dumped = dump_outputs(args.dump_outputs, tok, first) if args.dump_outputs and rank == 0 else None
     tot = eng.scan_totals()
     loop_t = None
     if timing:
@@ -651,6 +723,8 @@ def main() -> None:
             "legs": legs,
             "roofline_bw": bw,
         }
+        if dumped is not None:
+            out["dumped_outputs"] = dumped
         if world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(X.numpy(), device)
             out["speedup_vs_cpu_baseline"] = out["value"] / out["cpu_baseline"]["value"]
