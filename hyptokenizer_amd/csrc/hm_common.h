@@ -49,6 +49,7 @@ typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 #define HM_MODE_HIST 2
 #define HM_HIST_BINS 256
 #define HM_DIGIT_BINS 4096
+#define HM_EXACT_BINS 2048            // hm_exact.hip: bins of one digit of the distance bits (11 + 11 + 10)
 #define HM_RANK_LIMIT 49152        // rank sort is O(M^2): narrow by radix digits above this
 #define HM_TAIL_BLOCKS 32          // blocks of the argmin tail kernel (one is enough for <= HM_TAIL_SOLO entries)
 #define HM_TAIL_THREADS 1024
@@ -141,6 +142,7 @@ struct HostCtl {                 // pinned host mirror of small device results
     ArgminRec rec2[2];           // [0] record, [1].found / .dbits = emitted count (low / high)
     ArgminRec loop_recs[HM_LOOP_MAX_STEPS];
     uint32_t hist[HM_DIGIT_BINS];
+    unsigned long long xhist[HM_EXACT_BINS];   // hm_exact.hip: one bin can hold more than 2^32 pairs (a tie flood)
 };
 
 // state of the device-resident merge loops (one per engine, in HBM)
@@ -201,6 +203,7 @@ struct hm_engine {
     bool force_exact = false;                   // knob exact_search
     float topk_exact_thr = 0.0f;                // > 0: whole searches at thresholds >= this one go straight to the exact path (hm_exact.hip)
     uint32_t* d_rowcnt = nullptr;               // hm_exact.hip: per-row counts (allocated on first use)
+    unsigned long long* d_xhist = nullptr;      // hm_exact.hip: 64-bit digit histogram, HM_EXACT_BINS (allocated on first use)
     LoopState* h_loop = nullptr;                // pinned host image of a LoopState: the incremental loop's initial state goes up, and its final state comes back, in ONE copy each
     bool force_f32 = false;
     bool armed = false;

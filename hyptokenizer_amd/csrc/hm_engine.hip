@@ -213,7 +213,7 @@ extern "C" int hm_engine_destroy(hm_engine* e)
     (void)hipSetDevice(e->device);
     (void)hm_comm_destroy(e);
     void* dev_ptrs[] = {e->img, e->ent, e->ent2, e->sorted, e->d_ctr, e->d_ctr64, e->d_rec, e->d_hist, e->d_rmax2_mem, e->d_parts,
-                        e->img16, e->d_seed, e->d_loop_recs, e->d_loop, e->d_len, e->d_prev, e->d_batch, e->d_rowkey, e->d_rowcnt, e->d_queue};
+                        e->img16, e->d_seed, e->d_loop_recs, e->d_loop, e->d_len, e->d_prev, e->d_batch, e->d_rowkey, e->d_rowcnt, e->d_xhist, e->d_queue};
     for (void* q : dev_ptrs)
         if (q) (void)hipFree(q);
     if (e->h) (void)hipHostFree(e->h);

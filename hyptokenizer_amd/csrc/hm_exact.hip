@@ -22,7 +22,6 @@
 #pragma clang fp contract(off)
 
 #define HM_EXACT_WAVES 3            // partner tiles per block; LDS = (1 + HM_EXACT_WAVES) row tiles + the histogram
-#define HM_EXACT_BINS 2048
 
 struct ExactArgs {
     const float* img;
@@ -36,9 +35,9 @@ struct ExactArgs {
     int shift, nbits;               //         digit = (bits >> shift) & ((1 << nbits) - 1)
     uint32_t bstar;
     int istar;                      // pass 2: bits < bstar, or bits == bstar and i <= istar
-    uint32_t* hist;                 // [HM_EXACT_BINS]
+    unsigned long long* hist;       // [HM_EXACT_BINS]: 64-bit, one bin can hold all C(131 072, 2) > 2^32 pairs
     unsigned long long* total;      // pass 0, may be NULL: pairs with d < thr
-    uint32_t* rowcnt;               // pass 1: [n]
+    uint32_t* rowcnt;               // pass 1: [n]; one row has fewer than 131 072 pairs
     uint4* ent;
     unsigned long long* emitted;
     uint32_t cap;
@@ -51,6 +50,7 @@ __global__ __launch_bounds__(64 * HM_EXACT_WAVES) void hm_exact_scan_kernel(cons
     const int tile_floats = HM_TILE_ROWS * a.RS;
     float* fixed = lds;                                          // 64 rows i, image layout
     float* tile = lds + (1 + wv) * tile_floats;                  // this wave's 64 partner rows j
+    // 32-bit LDS bins: one block sees at most 64 rows x HM_EXACT_WAVES x 64 partners = 12 288 pairs
     uint32_t* lhist = reinterpret_cast<uint32_t*>(lds + (1 + HM_EXACT_WAVES) * tile_floats);
     const int ti = a.ti0 + (int)blockIdx.y;
     const int tj = ti + (int)blockIdx.x * HM_EXACT_WAVES + wv;   // partner tiles start at the diagonal tile
@@ -113,7 +113,7 @@ __global__ __launch_bounds__(64 * HM_EXACT_WAVES) void hm_exact_scan_kernel(cons
         if (a.total != nullptr && lane == 0 && below_thr != 0ull) atomicAdd(a.total, below_thr);
         __syncthreads();
         for (int q = threadIdx.x; q < HM_EXACT_BINS; q += blockDim.x)
-            if (lhist[q]) atomicAdd(&a.hist[q], lhist[q]);
+            if (lhist[q]) atomicAdd(&a.hist[q], (unsigned long long)lhist[q]);
     }
 }
 
@@ -153,13 +153,14 @@ int hm_topk_exact(hm_engine* e, float c, float thr, int64_t k, int64_t row_begin
     if (row_end > n - 1) row_end = n - 1;
     if (n < 2 || row_begin >= row_end || !(thr > 0.0f)) return HM_OK;
     if (!e->d_rowcnt) HM_HIP(hipMalloc(&e->d_rowcnt, sizeof(uint32_t) * (size_t)e->max_rows));
+    if (!e->d_xhist) HM_HIP(hipMalloc(&e->d_xhist, sizeof(unsigned long long) * HM_EXACT_BINS));
     ExactArgs a;
     memset(&a, 0, sizeof(a));
     a.img = e->img; a.RS = e->RS; a.d = e->d; a.sign_mode = e->sign_mode;
     a.sqrt_c = sqrtf(c); a.thr = thr;
     a.n = (int)n; a.row_begin = (int)row_begin; a.row_end = (int)row_end;
     a.ntj = (int)((n + HM_TILE_ROWS - 1) / HM_TILE_ROWS);
-    a.hist = e->d_hist; a.total = nullptr; a.rowcnt = e->d_rowcnt;
+    a.hist = e->d_xhist; a.total = nullptr; a.rowcnt = e->d_rowcnt;
     a.ent = e->ent; a.emitted = e->d_ctr64 + 2; a.cap = e->ent_cap;
     // ---- 1. the k-th smallest distance's bits ----
     static const int kShift[3] = {21, 10, 0}, kBits[3] = {11, 11, 10};
@@ -167,7 +168,7 @@ int hm_topk_exact(hm_engine* e, float c, float thr, int64_t k, int64_t row_begin
     int64_t want = k;
     uint32_t prefix = 0, mask = 0;
     for (int level = 0; level < 3; ++level) {
-        HM_HIP(hipMemsetAsync(e->d_hist, 0, sizeof(uint32_t) * HM_EXACT_BINS, s));
+        HM_HIP(hipMemsetAsync(e->d_xhist, 0, sizeof(unsigned long long) * HM_EXACT_BINS, s));
         a.pass = 0; a.prefix = prefix; a.prefix_mask = mask; a.shift = kShift[level]; a.nbits = kBits[level];
         a.total = nullptr;
         if (level == 0) {
@@ -176,7 +177,7 @@ int hm_topk_exact(hm_engine* e, float c, float thr, int64_t k, int64_t row_begin
         }
         int rc = hm_exact_launch(e, a, s);
         if (rc) return rc;
-        HM_HIP(hipMemcpyAsync(e->h->hist, e->d_hist, sizeof(uint32_t) * HM_EXACT_BINS, hipMemcpyDeviceToHost, s));
+        HM_HIP(hipMemcpyAsync(e->h->xhist, e->d_xhist, sizeof(unsigned long long) * HM_EXACT_BINS, hipMemcpyDeviceToHost, s));
         if (level == 0) HM_HIP(hipMemcpyAsync(e->h->ctr64, e->d_ctr64, sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
         HM_HIP(hipStreamSynchronize(s));
         if (level == 0) {
@@ -190,8 +191,8 @@ int hm_topk_exact(hm_engine* e, float c, float thr, int64_t k, int64_t row_begin
         uint32_t dsel = nb - 1;
         match = 0;
         for (uint32_t q = 0; q < nb; ++q) {
-            if (cum + e->h->hist[q] >= (uint64_t)want) { dsel = q; match = e->h->hist[q]; break; }
-            cum += e->h->hist[q];
+            if (cum + e->h->xhist[q] >= (uint64_t)want) { dsel = q; match = e->h->xhist[q]; break; }
+            cum += e->h->xhist[q];
         }
         below = cum;
         prefix |= dsel << kShift[level];

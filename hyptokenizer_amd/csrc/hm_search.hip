@@ -1060,6 +1060,60 @@ extern "C" int hm_pairwise_count(hm_engine* e, float c, float thr, int64_t n_lim
     return HM_OK;
 }
 
+// valid entries of the listing in e->ent (m emitted) -> host triples out[0, min(valid, room))
+static int hm_copy_valid(hm_engine* e, const uint4* res, int64_t valid, int64_t room, int32_t* i_out, int32_t* j_out, float* d_out,
+                         int64_t* ncopy, hipStream_t s)
+{
+    const uint32_t m = (uint32_t)std::min<uint64_t>(e->h->ctr64[2], e->ent_cap);
+    HM_HIP(hipMemsetAsync(e->d_ctr + 3, 0, sizeof(uint32_t), s));
+    hipLaunchKernelGGL(hm_compact_valid_kernel, dim3(1024), dim3(256), 0, s, res, m, e->ent2, e->d_ctr + 3, e->ent_cap);
+    HM_HIP(hipGetLastError());
+    *ncopy = std::min<int64_t>(valid, room);
+    std::vector<uint4> host((size_t)*ncopy);
+    HM_HIP(hipMemcpyAsync(host.data(), e->ent2, sizeof(uint4) * (size_t)*ncopy, hipMemcpyDeviceToHost, s));
+    HM_HIP(hipStreamSynchronize(s));
+    for (int64_t t = 0; t < *ncopy; ++t) {
+        union { uint32_t u; float f; } cv; cv.u = host[(size_t)t].x;
+        d_out[t] = cv.f; i_out[t] = (int32_t)host[(size_t)t].y; j_out[t] = (int32_t)host[(size_t)t].z;
+    }
+    return HM_OK;
+}
+
+// More candidates in the range than the emission buffer holds (a tie flood: up to C(131 072, 2) > 2^32 pairs at distance 0):
+// the exact number from a pure count, and min(cap, count) candidates listed slab of rows by slab of rows in row order.  A
+// slab of at most ent_cap pairs cannot overflow the buffer; one row (< max_rows pairs) always fits it.
+static int hm_candidates_by_rows(hm_engine* e, float c, float thr, int64_t row_begin, int64_t row_end, int64_t cap,
+                                 int32_t* i_out, int32_t* j_out, float* d_out, int64_t* total, hipStream_t s)
+{
+    const int64_t n = e->n;
+    const int64_t r0 = std::max<int64_t>(row_begin, 0), r1 = (row_end < 0 || row_end > n - 1) ? n - 1 : row_end;
+    int64_t valid = 0, cnt = 0;
+    uint4* res = nullptr;
+    int rc = hm_topk_core(e, c, thr, 0, r0, r1, false, true, -1, &valid, &cnt, &res, s);
+    if (rc) return rc;
+    *total = cnt;
+    const int64_t want = std::min<int64_t>(cap, cnt);
+    int64_t got = 0;
+    for (int64_t lo = r0; lo < r1 && got < want;) {
+        int64_t hi = lo + 1, step = 1;
+        while (step > 0) {                                   // largest hi <= r1 with at most ent_cap pairs in [lo, hi)
+            if (hi + step <= r1 && hm_pairs_in_range(n, lo, hi + step) <= (int64_t)e->ent_cap) { hi += step; step *= 2; }
+            else step /= 2;
+        }
+        rc = hm_topk_core(e, c, thr, 0, lo, hi, true, true, -1, &valid, &cnt, &res, s);
+        if (rc) return rc;
+        if (res && valid > 0) {
+            int64_t ncopy = 0;
+            rc = hm_copy_valid(e, res, valid, want - got, i_out + got, j_out + got, d_out + got, &ncopy, s);
+            if (rc) return rc;
+            got += ncopy;
+        }
+        lo = hi;
+    }
+    if (got != want) return hm_fail(e, HM_E_STATE, "candidate listing: the row slabs disagree with the count");
+    return HM_OK;
+}
+
 extern "C" int hm_pairwise_candidates(hm_engine* e, float c, float thr, int64_t row_begin, int64_t row_end, int64_t cap,
                                       int32_t* i_out, int32_t* j_out, float* d_out, int64_t* total, void* stream)
 {
@@ -1074,22 +1128,12 @@ extern "C" int hm_pairwise_candidates(hm_engine* e, float c, float thr, int64_t 
     int64_t valid = 0, cnt = 0;
     uint4* res = nullptr;
     int rc = hm_topk_core(e, c, thr, 0, row_begin, row_end, true, true, -1, &valid, &cnt, &res, s);
+    if (rc == HM_E_CAPACITY) return hm_candidates_by_rows(e, c, thr, row_begin, row_end, cap, i_out, j_out, d_out, total, s);
     if (rc) return rc;
     *total = cnt;
     if (!res || valid == 0 || cap == 0) return HM_OK;
-    const uint32_t m = (uint32_t)std::min<uint64_t>(e->h->ctr64[2], e->ent_cap);
-    HM_HIP(hipMemsetAsync(e->d_ctr + 3, 0, sizeof(uint32_t), s));
-    hipLaunchKernelGGL(hm_compact_valid_kernel, dim3(1024), dim3(256), 0, s, res, m, e->ent2, e->d_ctr + 3, e->ent_cap);
-    HM_HIP(hipGetLastError());
-    const int64_t ncopy = std::min<int64_t>(valid, cap);
-    std::vector<uint4> host((size_t)ncopy);
-    HM_HIP(hipMemcpyAsync(host.data(), e->ent2, sizeof(uint4) * (size_t)ncopy, hipMemcpyDeviceToHost, s));
-    HM_HIP(hipStreamSynchronize(s));
-    for (int64_t t = 0; t < ncopy; ++t) {
-        union { uint32_t u; float f; } cv; cv.u = host[(size_t)t].x;
-        d_out[t] = cv.f; i_out[t] = (int32_t)host[(size_t)t].y; j_out[t] = (int32_t)host[(size_t)t].z;
-    }
-    return HM_OK;
+    int64_t ncopy = 0;
+    return hm_copy_valid(e, res, valid, cap, i_out, j_out, d_out, &ncopy, s);
 }
 
 extern "C" int hm_row_argmin(hm_engine* e, int64_t row, int64_t n_partners, float c, float thr, float* d, int32_t* i, int32_t* j,

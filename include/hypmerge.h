@@ -99,7 +99,7 @@ int hm_pairwise_argmin_dev(hm_engine* e, float c, float thr, int64_t row_begin, 
  * d_out/i_out/j_out have room for k entries (may be NULL when k == 0); *n_out = min(k, *count).
  * Replaces: the recompute branch of _find_merge_candidates_fast + candidates.sort() +
  * AdaptiveMergeCache.add_batch truncation to max_size (fast_hyperbolic_merge.py:336-355,371-374,78-95).
- * Always answers for k <= 65536: a table whose distances are so concentrated that no emission cut of the matrix-core
+ * Always answers for k <= 65536, at any pair count: a table whose distances are so concentrated that no emission cut of the matrix-core
  * prefilter fits the engine's buffers (all u within a few hundred ulps of 1) is searched by evaluating every pair in the
  * canonical arithmetic and selecting by counting (hm_exact.hip) -- like the reference, only slower than the usual path
  * (56 ms at 25 000 rows).  The same holds for hm_pairwise_argmin, hm_pairwise_topk_nocount and hm_pairwise_count. */
@@ -125,8 +125,8 @@ int hm_topk_refresh_end(hm_engine* e, float* d_out, int32_t* i_out, int32_t* j_o
  * appended, so this is len(candidates) of the search that ran when the table had n_limit rows. */
 int hm_pairwise_count(hm_engine* e, float c, float thr, int64_t n_limit, int64_t* count, void* stream);
 
-/* All candidates (unordered) -- the caller sorts them row-major.  At most cap triples are written;
- * *total is the exact number.  Replaces: the candidate list of _find_merge_candidates
+/* All candidates (unordered) -- the caller sorts them row-major.  min(cap, *total) triples are written;
+ * *total is the exact number (also past the emission buffer: the triples are then taken from the first rows).  Replaces: the candidate list of _find_merge_candidates
  * (hyperbolic_merge.py:247-269) when a caller really wants every tuple. */
 int hm_pairwise_candidates(hm_engine* e, float c, float thr, int64_t row_begin, int64_t row_end,
                            int64_t cap, int32_t* i_out, int32_t* j_out, float* d_out, int64_t* total,

@@ -312,6 +312,23 @@ def test_device_record_and_world1_nccl_shard(oracle):
         assert da == 0 and ra[0][0] == 0 and all(r[0] == 3 for r in ra[1:])
         eng.comm_destroy()
         assert eng.comm_info() is None
+        # a count past 2^32 through the exchange (its header carries the count in two words): literal sign mode, every
+        # one of C(92 683, 2) = 2^32 + 55 607 pairs at distance 0, the list in row-major order
+        n3 = 92683
+        t3 = torch.zeros((n3, 17), device="cuda")
+        t3[:] = lorentz_table(n3, 16, seed=5, scale=0.05).cuda()
+        eng3 = MergeEngine(n3, 17, "reference")
+        eng3.set_table(t3, n3)
+        eng3.comm_init()
+        gd, gi, gj, gc = eng3.global_topk(1.0, 0.1, 10000)
+        assert gc == n3 * (n3 - 1) // 2 and gc >> 32 == 1
+        hd, hi, hj, hc = eng3.topk(1.0, 0.1, 10000)
+        assert hc == gc and np.array_equal(gi, hi) and np.array_equal(gj, hj) and np.array_equal(bits(gd), bits(hd))
+        assert np.array_equal(gi, np.zeros(10000, np.int32)) and np.array_equal(gj, np.arange(1, 10001, dtype=np.int32))
+        assert not bits(gd).any()
+        assert eng3.global_argmin(1.0, 0.1) == eng3.argmin(1.0, 0.1) == (0.0, 0, 1)
+        eng3.comm_destroy()
+        eng3.close()
     finally:
         dist.destroy_process_group()
 
