@@ -73,6 +73,22 @@ __device__ __forceinline__ int hm_pos_in_group(int s) { return ((s & 1) << 1) | 
 // offset of spatial coordinate s inside an fp32 image row
 __device__ __forceinline__ int hm_img_off(int s) { return 4 * (s >> 2) + hm_pos_in_group(s & 3); }
 
+// The pair scan's argmin running key is (bits(u') << 32) | low, low = hm_key_low(i, j): a 32-bit word monotone in (i, j)
+// and never above the row-major order, so a coarser word only lets more zero-distance ties through its `<=` tests.  With
+// ib = max(17, ceil(log2(max_rows))) row-index bits, i keeps all of its bits and j its ib - (2 ib - 32) top bits:
+//   ib = 17 (max_rows <= 131 072, the narrow key): (i << 15) | (j >> 2)
+//   ib = 20 (max_rows <= 2^20):                    (i << 12) | (j >> 8)
+// No code decodes i or j from the key: the answer always comes from the exact re-evaluation of the emitted entries.
+#define HM_KEY_IB_NARROW 17
+#define HM_MAX_TABLE_ROWS (1 << 20)
+__host__ __device__ constexpr int hm_key_ib(int64_t max_rows)
+{
+    int ib = HM_KEY_IB_NARROW;
+    while (((int64_t)1 << ib) < max_rows) ++ib;
+    return ib;
+}
+__host__ __device__ __forceinline__ uint32_t hm_key_low(uint32_t i, uint32_t j, int si, int sj) { return (i << si) | (j >> sj); }
+
 struct ScanArgs {
     const float* img;
     const unsigned char* img16;   // bf16 image (BF = 1 kernels)
@@ -125,6 +141,9 @@ struct ScanArgs {
     int n_items;
     unsigned long long q_tag;
     unsigned long long* q_ctr;
+    // ARGMIN mode: shift amounts of the engine's running-key layout (hm_key_low); read by the wide-key kernels only
+    int key_wide;                 // host-side: the engine's key has more than 17 row-index bits
+    int key_si, key_sj;
 };
 
 // Seed of the argmin search's running key, kept on the device between searches: the key of the last
@@ -183,6 +202,7 @@ struct hm_engine {
     int d1 = 0, d = 0, NG = 0, RS = 0, sign_mode = 0;
     float* img = nullptr;
     unsigned char* img16 = nullptr;
+    int key_ib = HM_KEY_IB_NARROW;        // row-index bits of the argmin running key (hm_key_low), fixed by max_rows
     int KC = 0, RB16 = 0;                 // chunks of 8 K-slots and bytes per bf16 image row
     int precision = HM_PREFILTER_AUTO;
     bool bf16_ok = true;                  // false: no bf16 image for this width (d > 124)

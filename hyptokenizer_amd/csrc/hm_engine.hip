@@ -148,8 +148,8 @@ extern "C" int hm_engine_create(hm_engine** out, int device, int64_t max_rows, i
     if (!out) return hm_fail(nullptr, HM_E_ARG, "hm_engine_create: out is NULL");
     *out = nullptr;
     if (d1 < 2 || d1 > 129) return hm_fail(nullptr, HM_E_ARG, "hm_engine_create: d1 must be in [2, 129]");
-    if (max_rows < 2 || max_rows > 131072)
-        return hm_fail(nullptr, HM_E_ARG, "hm_engine_create: max_rows must be in [2, 131072]");
+    if (max_rows < 2 || max_rows > HM_MAX_TABLE_ROWS)
+        return hm_fail(nullptr, HM_E_ARG, "hm_engine_create: max_rows must be in [2, 1048576]");
     if (sign_mode != 0 && sign_mode != 1) return hm_fail(nullptr, HM_E_ARG, "hm_engine_create: sign_mode must be 0 or 1");
     if (prefilter < HM_PREFILTER_AUTO || prefilter > HM_PREFILTER_BF16)
         return hm_fail(nullptr, HM_E_ARG, "hm_engine_create: prefilter must be HM_PREFILTER_AUTO / _F32 / _BF16");
@@ -162,6 +162,7 @@ extern "C" int hm_engine_create(hm_engine** out, int device, int64_t max_rows, i
     hm_engine* e = new hm_engine();
     e->device = device;
     e->max_rows = max_rows;
+    e->key_ib = hm_key_ib(max_rows);     // 17 (the narrow key) up to 131 072 rows
     e->d1 = d1;
     e->d = d1 - 1;
     e->NG = hm_pick_ng(e->d);

@@ -37,7 +37,7 @@ struct ExactArgs {
     int istar;                      // pass 2: bits < bstar, or bits == bstar and i <= istar
     unsigned long long* hist;       // [HM_EXACT_BINS]: 64-bit, one bin can hold all C(131 072, 2) > 2^32 pairs
     unsigned long long* total;      // pass 0, may be NULL: pairs with d < thr
-    uint32_t* rowcnt;               // pass 1: [n]; one row has fewer than 131 072 pairs
+    uint32_t* rowcnt;               // pass 1: [n]; one row has fewer than 2^20 pairs
     uint4* ent;
     unsigned long long* emitted;
     uint32_t cap;

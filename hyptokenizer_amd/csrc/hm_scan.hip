@@ -80,7 +80,8 @@ __device__ __forceinline__ void hm_dma_run(const char* src, uint32_t dst)
 #ifndef HM_SCAN_DEEP_PREFETCH
 #define HM_SCAN_DEEP_PREFETCH 1
 #endif
-template <int NG, int SIGN, int MODE, int BF, int TM, int WPB, int SUB>
+// WK (ARGMIN mode only): the engine's running key is wide -- shift amounts from ScanArgs; narrow: (i << 15) | (j >> 2)
+template <int NG, int SIGN, int MODE, int BF, int TM, int WPB, int SUB, bool WK = false>
 __global__ __launch_bounds__(64 * WPB, 2) void hm_scan_kernel(const ScanArgs p)
 {
     static_assert(SUB % 2 == 0, "the two accumulator sets alternate between column groups: an even number per tile");
@@ -140,6 +141,8 @@ __global__ __launch_bounds__(64 * WPB, 2) void hm_scan_kernel(const ScanArgs p)
     const float zmax_f = 1.0f - delta;               // u_f at or below this: canonical u <= 1, d == 0
     const bool cut_all = (p.cut_bits == 0xffffffffu);
     const float cut_f = cut_all ? p.u_hi : hm::bitsf(p.cut_bits) + delta;
+    static_assert(!WK || MODE == HM_MODE_ARGMIN, "only the argmin search keeps a running key");
+    const int key_si = WK ? p.key_si : 32 - HM_KEY_IB_NARROW, key_sj = WK ? p.key_sj : 2 * HM_KEY_IB_NARROW - 32;
 
     // the running argmin key as it stands when the block starts (seeded, or found by earlier blocks)
     if (MODE == HM_MODE_ARGMIN) {
@@ -380,7 +383,7 @@ __global__ __launch_bounds__(64 * WPB, 2) void hm_scan_kernel(const ScanArgs p)
             // certainly at distance 0 too is only emitted when its (i, j) orders before the best's (`low <= best_low`
             // below); every pair of this group has low >= lowmin.  So when the whole group is certainly-zero and starts
             // behind the best pair, the slow path would emit nothing: skip it (1.6 ms -> 0.3 ms per tie-flood scan).
-            const uint32_t lowmin = ((uint32_t)i0w << 15) | ((uint32_t)j0s >> 2);
+            const uint32_t lowmin = hm_key_low((uint32_t)i0w, (uint32_t)j0s, key_si, key_sj);
             if (lowmin > best_low) {
                 float worst = SIGN ? -acc[set][0][0] : acc[set][0][0];          // the LARGEST u of the lane's elements
 #pragma unroll
@@ -447,7 +450,7 @@ __global__ __launch_bounds__(64 * WPB, 2) void hm_scan_kernel(const ScanArgs p)
                     emit = zero ? (i <= p.tie_imax) : ((!sure && p.count_sure) || cut_all || up <= cutv);
                 } else {
                     const uint32_t ubz = zero ? 0x3f7fffffu : ub;
-                    const uint32_t low = ((uint32_t)i << 15) | ((uint32_t)j >> 2);
+                    const uint32_t low = hm_key_low((uint32_t)i, (uint32_t)j, key_si, key_sj);
                     emit = !(zero && best_bits == 0x3f7fffffu) || (low <= best_low);
                     if (emit && !write) {
                         const unsigned long long k = ((unsigned long long)ubz << 32) | low;
@@ -686,7 +689,7 @@ __global__ __launch_bounds__(64 * WPB, 2) void hm_scan_kernel(const ScanArgs p)
 // ------------------------------------------------------------------------------------------------
 // launch
 // ------------------------------------------------------------------------------------------------
-template <int NG, int SIGN, int MODE, int BF, int TM, int WPB, int SUB>
+template <int NG, int SIGN, int MODE, int BF, int TM, int WPB, int SUB, bool WK = false>
 static hipError_t hm_launch_scan_t(hm_engine* e, const ScanArgs& a, dim3 grid, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1)
 {
     const size_t row_bytes = BF ? 16 * hm_row16_chunks(NG) : 4 * hm_row_floats(NG);
@@ -696,7 +699,7 @@ static hipError_t hm_launch_scan_t(hm_engine* e, const ScanArgs& a, dim3 grid, h
     lds += (size_t)32 * row_bytes;                                          // slack behind the ring: the early request of "the next group's" fragment
     if (MODE == HM_MODE_HIST) lds += sizeof(uint32_t) * HM_HIST_BINS;      // (HIST mode keeps its bins there; they are only read by that request)
     lds += 16;                                                              // the item queue's broadcast word
-    const void* fn = reinterpret_cast<const void*>(&hm_scan_kernel<NG, SIGN, MODE, BF, TM, WPB, SUB>);
+    const void* fn = reinterpret_cast<const void*>(&hm_scan_kernel<NG, SIGN, MODE, BF, TM, WPB, SUB, WK>);
     if (lds > 48 * 1024 && e->attr_done.find(fn) == e->attr_done.end()) {     // per engine (= per device), not process-wide
         hipError_t st = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (st != hipSuccess) return st;
@@ -725,8 +728,8 @@ static hipError_t hm_launch_scan_t(hm_engine* e, const ScanArgs& a, dim3 grid, h
             b.q_ctr = e->d_queue + 16 * ((b.ctr64 == e->d_ctr64) ? 0 : 1);      // one word per counter set (the pipelined loop alternates them)
         }
     }
-    if (ev0 != nullptr || ev1 != nullptr) hipExtLaunchKernelGGL((hm_scan_kernel<NG, SIGN, MODE, BF, TM, WPB, SUB>), grid, dim3(64 * WPB), lds, s, ev0, ev1, 0, b);
-    else hipLaunchKernelGGL((hm_scan_kernel<NG, SIGN, MODE, BF, TM, WPB, SUB>), grid, dim3(64 * WPB), lds, s, b);
+    if (ev0 != nullptr || ev1 != nullptr) hipExtLaunchKernelGGL((hm_scan_kernel<NG, SIGN, MODE, BF, TM, WPB, SUB, WK>), grid, dim3(64 * WPB), lds, s, ev0, ev1, 0, b);
+    else hipLaunchKernelGGL((hm_scan_kernel<NG, SIGN, MODE, BF, TM, WPB, SUB, WK>), grid, dim3(64 * WPB), lds, s, b);
     return hipGetLastError();
 }
 
@@ -736,11 +739,17 @@ static hipError_t hm_launch_scan_ng(hm_engine* e, int sign, int mode, const Scan
 {
     if (sign) {
         if (mode == HM_MODE_TOPK) return hm_launch_scan_t<NG, 1, HM_MODE_TOPK, BF, TM, WPB, SUB>(e, a, grid, s, ev0, ev1);
-        if (mode == HM_MODE_ARGMIN) return hm_launch_scan_t<NG, 1, HM_MODE_ARGMIN, BF, TM, WPB, SUB>(e, a, grid, s, ev0, ev1);
+        if (mode == HM_MODE_ARGMIN) {
+            if (a.key_wide) return hm_launch_scan_t<NG, 1, HM_MODE_ARGMIN, BF, TM, WPB, SUB, true>(e, a, grid, s, ev0, ev1);
+            return hm_launch_scan_t<NG, 1, HM_MODE_ARGMIN, BF, TM, WPB, SUB>(e, a, grid, s, ev0, ev1);
+        }
         return hm_launch_scan_t<NG, 1, HM_MODE_HIST, BF, TM, WPB, SUB>(e, a, grid, s, ev0, ev1);
     }
     if (mode == HM_MODE_TOPK) return hm_launch_scan_t<NG, 0, HM_MODE_TOPK, BF, TM, WPB, SUB>(e, a, grid, s, ev0, ev1);
-    if (mode == HM_MODE_ARGMIN) return hm_launch_scan_t<NG, 0, HM_MODE_ARGMIN, BF, TM, WPB, SUB>(e, a, grid, s, ev0, ev1);
+    if (mode == HM_MODE_ARGMIN) {
+        if (a.key_wide) return hm_launch_scan_t<NG, 0, HM_MODE_ARGMIN, BF, TM, WPB, SUB, true>(e, a, grid, s, ev0, ev1);
+        return hm_launch_scan_t<NG, 0, HM_MODE_ARGMIN, BF, TM, WPB, SUB>(e, a, grid, s, ev0, ev1);
+    }
     return hm_launch_scan_t<NG, 0, HM_MODE_HIST, BF, TM, WPB, SUB>(e, a, grid, s, ev0, ev1);
 }
 
@@ -855,6 +864,9 @@ bool hm_prepare_scan(hm_engine* e, const Bounds& b, int64_t row_begin, int64_t r
     a.sample_stride = 1;
     a.rmax2_bits = e->d_rmax2;
     a.stop = nullptr;
+    a.key_wide = e->key_ib > HM_KEY_IB_NARROW ? 1 : 0;
+    a.key_si = 32 - e->key_ib;
+    a.key_sj = 2 * e->key_ib - 32;
     const int rb_last = (int)((row_end - 1) / block_rows);
     const int nrb = rb_last - a.rb_first + 1;
     // diagonal advance per row block in tiles (rounded down: the kernel clamps to the exact diagonal)

@@ -28,6 +28,7 @@ struct TailArgs {
     int bf, kterms;
     uint32_t* rmax2_bits;
     int arm, arm_rb, arm_re;         // leave counters + running key ready for the next search of rows [arm_rb, arm_re)
+    int key_si, key_sj;              // the engine's running-key layout (hm_key_low)
     MergeFuse mf;
 };
 
@@ -135,7 +136,7 @@ __global__ __launch_bounds__(HM_TAIL_THREADS) void hm_argmin_tail_kernel(const T
             // prefilter value is <= u_c + delta, and an entry the scan skips on this key has u_f >= u_c + 3 delta, so it
             // cannot order before the pair -- or, for a pair at distance 0 (u_c <= 1), the exact zero-class key
             const float u = hm_img_u_halfwave(a.img, a.RS, a.d, bi, bj, a.sign_mode, lane);
-            if (u <= 1.0f) seed_key = (0x3f7fffffull << 32) | (unsigned long long)((bi << 15) | (bj >> 2));
+            if (u <= 1.0f) seed_key = (0x3f7fffffull << 32) | (unsigned long long)hm_key_low(bi, bj, a.key_si, a.key_sj);
             else seed_key = ((unsigned long long)hm::fbits(u + hm_scan_delta(a.bf != 0, a.kterms, a.rmax2_bits)) << 32) | 0xffffffffull;
             seed_row = bi;
             if (lane == 0) { a.seed->key = seed_key; a.seed->i = bi; a.seed->valid = 1u; }
@@ -185,6 +186,7 @@ int hm_launch_argmin_tail(hm_engine* e, const ScanArgs& sa, float sqrt_c, float 
     t.seed = with_seed ? e->d_seed : nullptr;
     t.bf = sa.bf16; t.kterms = sa.bf16 ? 8 * e->KC : e->RS; t.rmax2_bits = e->d_rmax2;
     t.arm = arm ? 1 : 0; t.arm_rb = arm_rb; t.arm_re = arm_re;
+    t.key_si = 32 - e->key_ib; t.key_sj = 2 * e->key_ib - 32;
     t.mf = mf;
     // Pipelined loop (mf.rowkey set): the kernel runs UNDER the next step's scan, whose two blocks per CU leave room for four
     // more waves at most -- 256-thread blocks; otherwise 1024
@@ -525,6 +527,9 @@ static int hm_estimate_cut(hm_engine* e, ScanArgs a, dim3 grid, int64_t target, 
     uint32_t hi_bits = hi.f == INFINITY ? 0x7f800000u : hi.u;
     int stride = 1;
     while (stride < 64 && pairs / (stride * 2) > 40000000) stride *= 2;
+    // past C(131 072, 2) pairs: a tie flood puts every sample into one 32-bit bin -- at most ~pairs / stride of them (plus
+    // one tile per row block), so the stride keeps growing until that stays below 2^30
+    while (pairs / stride > ((int64_t)1 << 30)) stride *= 2;
     double base = 0.0;               // estimated entries below the current zoom window
     for (int zoom = 0; zoom < 6; ++zoom) {
         uint32_t span = hi_bits - lo_bits;
@@ -555,7 +560,10 @@ static int hm_estimate_cut(hm_engine* e, ScanArgs a, dim3 grid, int64_t target, 
                 // value only for the first rows; rows are visited in row-major order by the selection.
                 const double per_row = ((double)e->h->hist[bsel] * stride) / (double)(a.row_end - a.row_begin);
                 double rows = ((double)target - before) / (per_row > 1e-9 ? per_row : 1e-9);
-                int64_t imax = a.row_begin + (int64_t)(rows * 2.0) + 64;
+                // (a slack of 64 rows, fewer where 64 rows of partners would fill more than half the buffer)
+                int64_t pad = 64;
+                while (pad > 1 && pad * (int64_t)a.n > (int64_t)e->ent_cap / 2) pad >>= 1;
+                int64_t imax = a.row_begin + (int64_t)(rows * 2.0) + pad;
                 if (imax > a.row_end) imax = a.row_end;
                 *tie_imax = (int)imax;
             }

@@ -21,7 +21,8 @@ from ._lib import SIGN_LORENTZ, SIGN_REFERENCE, HypMergeError, HypMergeUnavailab
 
 SIGN_MODES = {"reference": SIGN_REFERENCE, "lorentz": SIGN_LORENTZ}
 PREFILTERS = {"auto": _lib.PREFILTER_AUTO, "f32": _lib.PREFILTER_F32, "bf16": _lib.PREFILTER_BF16}
-MAX_ROWS = 131072        # hm_engine_create: largest table
+MAX_TABLE_ROWS = 1 << 20  # hm_engine_create: largest table
+MAX_ROWS = 131072        # largest table whose scan uses the narrow 17-bit key ((i << 15) | (j >> 2))
 MAX_WIDTH = 129          # ... and widest row (d + 1)
 
 

@@ -43,7 +43,7 @@ from tqdm import tqdm
 
 from ..embedding.lorentz_model import batch_distance, distance
 from .._lib import LOOP_MAX_STEPS
-from ..engine import MAX_ROWS, MAX_WIDTH, HypMergeUnavailable, MergeEngine, sign_mode_id
+from ..engine import MAX_TABLE_ROWS, MAX_WIDTH, HypMergeUnavailable, MergeEngine, sign_mode_id
 
 logger = logging.getLogger(__name__)
 
@@ -140,9 +140,9 @@ class HyperbolicTokenizer:
         sign_mode_id(sign_convention)
 
         width = embeddings.size(1)
-        if engine is None and (not 2 <= max_vocab_size <= MAX_ROWS or not 2 <= width <= MAX_WIDTH):
+        if engine is None and (not 2 <= max_vocab_size <= MAX_TABLE_ROWS or not 2 <= width <= MAX_WIDTH):
             # the reference accepts any size and fails (or thrashes) later; say it where the object is built
-            raise ValueError(f"the merge engine takes tables of 2..{MAX_ROWS} rows and 2..{MAX_WIDTH} columns "
+            raise ValueError(f"the merge engine takes tables of 2..{MAX_TABLE_ROWS} rows (MAX_TABLE_ROWS) and 2..{MAX_WIDTH} columns "
                              f"(max_vocab_size={max_vocab_size}, embedding width={width})")
         table = torch.zeros((max_vocab_size, width), dtype=embeddings.dtype, device=self.device)
         table[: self.current_vocab_size] = embeddings.detach().to(self.device)

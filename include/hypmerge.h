@@ -61,7 +61,10 @@ const char* hm_last_error(const hm_engine* e);          /* e may be NULL: last g
  * is allocated in the per-call path afterwards.
  * LIMITS (narrower than the reference, which takes any max_vocab_size; both are rejected here with HM_E_ARG, by the Python
  * classes at construction with a ValueError):
- *   2 <= max_rows <= 131072   -- a row index has 17 bits in the 32-bit (i, j) word of the pair scan's 64-bit running key;
+ *   2 <= max_rows <= 1048576  -- the pair scan's 64-bit argmin running key packs (i, j) into 32 bits with ib row-index bits,
+ *                                ib = max(17, ceil(log2(max_rows))): (i << (32 - ib)) | (j >> (2 ib - 32)).  Up to 131072
+ *                                rows that is the narrow key (i << 15) | (j >> 2); larger engines use the wide form, which
+ *                                only lets more zero-distance ties through to the exact re-evaluation;
  *   2 <= d1 = d + 1 <= 129    -- kernels are instantiated for d <= 128; the bf16 prefilter exists for d <= 124 (d + 4 K-slots
  *                                in at most 16 chunks of 8), wider tables use the fp32 prefilter.
  * Replaces: the pre-allocated table of HyperbolicTokenizer.__init__ (hyperbolic_merge.py:144-153)
