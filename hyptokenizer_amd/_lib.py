@@ -37,6 +37,8 @@ EXPORTED_SYMBOLS = (
     "hm_tokenize_table_capacity", "hm_tokenize_build_table", "hm_tokenize_batch", "hm_debug_time_loops", "hm_last_loop_timing", "hm_shard_loop_begin", "hm_shard_merge_step", "hm_shard_loop_end",
     "hm_topk_refresh_begin", "hm_topk_refresh_end", "hm_debug_set_knob", "hm_debug_set_default_knob",
     "hm_comm_unique_id", "hm_comm_init", "hm_comm_destroy", "hm_comm_info", "hm_shard_merge_steps", "hm_global_argmin", "hm_global_topk",
+    "hm_greedy_create", "hm_greedy_destroy", "hm_greedy_set_corpus", "hm_greedy_add_strings", "hm_greedy_count",
+    "hm_greedy_longest",
 )
 
 
@@ -100,6 +102,12 @@ def load() -> C.CDLL:
     L.hm_tokenize_table_capacity.argtypes = [i64]
     L.hm_tokenize_build_table.argtypes = [vp, vp, vp, i64, vp, i64]
     L.hm_tokenize_batch.argtypes = [vp, vp, vp, i64, vp, i64, vp, vp, vp, vp]
+    L.hm_greedy_create.argtypes = [C.POINTER(vp), C.c_int]
+    L.hm_greedy_destroy.argtypes = [vp]
+    L.hm_greedy_set_corpus.argtypes = [vp, vp, vp, vp, i64, vp]
+    L.hm_greedy_add_strings.argtypes = [vp, vp, vp, i64, vp]
+    L.hm_greedy_count.argtypes = [vp, vp, vp, i64, vp, vp, vp]
+    L.hm_greedy_longest.argtypes = [vp, vp, vp, vp]
     L.hm_comm_unique_id.argtypes = [vp]
     L.hm_comm_init.argtypes = [vp, vp, C.c_int, C.c_int]
     L.hm_comm_destroy.argtypes = [vp]

@@ -16,6 +16,8 @@ What runs where
   ~2.5 ms per candidate here (50 ``distance().item()`` calls); a refresh scores EVERY candidate.
 * **GPU (``hm_project_table``)** -- ``_project_embeddings`` (``:784-792``) over the whole table in
   place, scan images and norm bounds rebuilt in the same pass.
+* **GPU (``hm_greedy_count``)** -- the greedy longest-match counts behind the compression term (``:813-899``): all
+  cache entries a batch of candidates is missing, in one call (``greedy_matcher.GreedyMatcher``).
 * **host Python, reference order kept** -- everything that consumes an RNG or touches strings:
   ``torch.randperm`` per candidate (same call order, so the same samples), the frequency table,
   compression and morphology heuristics, phase logic, threshold dynamics, statistics sampling with
@@ -473,6 +475,47 @@ class EnhancedFastHyperbolicTokenizer(FastHyperbolicTokenizer):
         ratio = 1.0 if after == 0 else before / after
         return max(0.0, min(1.0, (ratio - 1.0) / 1.0))
 
+    def _prefill_compression_cache(self, pairs: List[Tuple[int, int]]) -> None:
+        """On a HIP device: every ``merge_{i}_{j}_{text[:20]}`` entry the host loop of ``_compute_compression_score``
+        would compute for ``pairs`` (the missing ones, inserted in the loop's order), from ONE ``hm_greedy_count`` call
+        over the representative lines of ``corpus_sample[:10]``.  The loop then only reads the cache.  Skipped when
+        the greedy tokenisation or the compression score is customised by a subclass or an instance."""
+        if not self.corpus_sample or self.device.type != "cuda":
+            return
+        cls, own = type(self), EnhancedFastHyperbolicTokenizer
+        if (cls._compute_compression_score is not own._compute_compression_score
+                or cls._tokenize_with_vocab is not own._tokenize_with_vocab
+                or {"_compute_compression_score", "_tokenize_with_vocab"} & set(self.__dict__)):
+            return
+        cache = self.tokenize_cache
+        if "original" not in cache:
+            cache["original"] = sum(len(self.tokenize(text)) for text in self.corpus_sample)
+        keys = [text[:20] for text in self.corpus_sample[:10]]
+        missing = [(a, b) for a, b in pairs if any(f"merge_{a}_{b}_{k}" not in cache for k in keys)]
+        if not missing:
+            return
+        index, reps = {}, []
+        for text, key in zip(self.corpus_sample, keys):
+            if key not in index:
+                index[key] = len(reps)
+                reps.append(text)
+        state = getattr(self, "_greedy_state", None)
+        if state is None:
+            from .greedy_matcher import GreedyMatcher
+            state = self._greedy_state = [GreedyMatcher(self.device), None]
+        matcher = state[0]
+        if state[1] != reps:
+            matcher.set_corpus(reps)
+            state[1] = reps
+        matcher.sync(self.vocab)
+        vocab = self.vocab
+        _, counts = matcher.count([vocab[a] + vocab[b] for a, b in missing], per_line=True)
+        for (a, b), row in zip(missing, counts.tolist()):
+            for key in keys:
+                name = f"merge_{a}_{b}_{key}"
+                if name not in cache:
+                    cache[name] = row[index[key]]
+
     # ------------------------------------------------------------------------------------------
     # combined score
     # ------------------------------------------------------------------------------------------
@@ -510,6 +553,8 @@ class EnhancedFastHyperbolicTokenizer(FastHyperbolicTokenizer):
             freq = self._frequency_scores(ii, jj)
             sem = self._semantic_coherence_batch(ii, jj)
         pairs = list(zip(ii.tolist(), jj.tolist()))
+        if self.use_compression_aware:
+            self._prefill_compression_cache(pairs)
         comp = [self._compute_compression_score(a, b) for a, b in pairs] if self.use_compression_aware \
             else [0.0] * count
         morph = [self._morphology_score(a, b) for a, b in pairs] if self.use_hierarchical else [0.0] * count

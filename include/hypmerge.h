@@ -287,6 +287,42 @@ int hm_tokenize_batch(const int32_t* sym_dev, const int64_t* offsets_dev, const 
                       const uint64_t* table_dev, int64_t capacity, int32_t* out_dev, int32_t* out_len_dev,
                       int32_t* passes_dev, void* stream);
 
+/* ---- greedy longest-match counter (compression-aware scoring) -----------------------------------------------
+ * Token counts of a corpus sample under "vocabulary + one candidate string" for K candidates at once, by the
+ * reference's greedy rule: at position p the longest vocabulary entry that is a prefix of text[p:], else text[p].
+ * Everything is Unicode code points (int32, Python str positions).  Empty strings never match (the reference's loop
+ * does not terminate on them).  Independent of any engine; errors are reported through hm_last_error(NULL).
+ * Inputs are HOST arrays (strings as code points concatenated + int64 offsets[count + 1], offsets[0] = 0); outputs
+ * are device arrays.  Every entry point synchronises `stream` before it returns.
+ * LIMITS (HM_E_ARG): corpus code points < 2^31 and lines < 2^31; vocabulary pool < 2^31 code points; candidate code
+ * points < 2^31, K < 2^31, lines * ceil(K / 64) < 2^31; every string shorter than 2^31; multiplicities >= 0.
+ *
+ * hm_greedy_create / hm_greedy_destroy: one matcher on device `device`.
+ * Replaces: the per-instance tokenize_cache machinery of CompressionAwareTokenizer (compression_aware_tokenizer.py:84-87). */
+typedef struct hm_greedy hm_greedy;
+int hm_greedy_create(hm_greedy** out, int device);
+int hm_greedy_destroy(hm_greedy* g);
+/* The corpus: n_lines lines (representative texts), mult[n_lines] >= 0 their multiplicities.  Rebuilds lm (longest
+ * vocabulary match per position) from every string added so far and the per-line base counts.
+ * Replaces: the iteration over self.corpus_sample (compression_aware_tokenizer.py:152-161; enhanced...:884-891), with
+ * lines that share their cache key merge_{i}_{j}_{text[:20]} folded into one line of multiplicity > 1. */
+int hm_greedy_set_corpus(hm_greedy* g, const int32_t* cps, const int64_t* offsets, const int64_t* mult, int64_t n_lines,
+                         void* stream);
+/* Append vocabulary strings (the vocabulary only ever grows: vocab.append in _merge_tokens, hyperbolic_merge.py:343-355).
+ * lm[p] = max(lm[p], |t|) wherever a new string t occurs; more than 64 strings at once rebuild lm through the hashed set.
+ * Replaces: temp_vocab = self.vocab.copy() + sorted(vocab, key=len) per candidate (compression_aware_tokenizer.py:148-150,
+ * :104-105). */
+int hm_greedy_add_strings(hm_greedy* g, const int32_t* cps, const int64_t* offsets, int64_t n_strings, void* stream);
+/* k candidate strings m_c: counts_dev[c * n_lines + l] (may be NULL) = greedy token count of line l under
+ * vocabulary + {m_c}; totals_dev[c] = sum_l mult[l] * counts[c][l].  HM_E_STATE before hm_greedy_set_corpus.
+ * Replaces: the per-candidate _tokenize_with_vocab loop (compression_aware_tokenizer.py:143-161, :91-120) and
+ * _compute_compression_score's (enhanced_fast_hyperbolic_merge.py:849-899). */
+int hm_greedy_count(hm_greedy* g, const int32_t* cps, const int64_t* offsets, int64_t k, int32_t* counts_dev,
+                    int64_t* totals_dev, void* stream);
+/* Copies of the matcher's lm[corpus code points] and base[n_lines] (either may be NULL).  No reference equivalent
+ * (inspection: the incremental lm equals a rebuild). */
+int hm_greedy_longest(hm_greedy* g, int32_t* lm_dev, int32_t* base_dev, void* stream);
+
 /* Dense distance block between two arbitrary device arrays: out_dev[n1, n2].
  * Replaces: batch_distance / batch_distance_optimized (embedding/lorentz_model.py:141-210) and
  * _compute_pairwise_distances (hyperbolic_merge.py:166-190).  Engine-independent. */
