@@ -38,7 +38,7 @@ EXPORTED_SYMBOLS = (
     "hm_topk_refresh_begin", "hm_topk_refresh_end", "hm_debug_set_knob", "hm_debug_set_default_knob",
     "hm_comm_unique_id", "hm_comm_init", "hm_comm_destroy", "hm_comm_info", "hm_shard_merge_steps", "hm_global_argmin", "hm_global_topk",
     "hm_greedy_create", "hm_greedy_destroy", "hm_greedy_set_corpus", "hm_greedy_add_strings", "hm_greedy_count",
-    "hm_greedy_longest",
+    "hm_greedy_longest", "hm_pairfreq_create", "hm_pairfreq_destroy", "hm_pairfreq_add", "hm_pairfreq_read",
 )
 
 
@@ -108,6 +108,10 @@ def load() -> C.CDLL:
     L.hm_greedy_add_strings.argtypes = [vp, vp, vp, i64, vp]
     L.hm_greedy_count.argtypes = [vp, vp, vp, i64, vp, vp, vp]
     L.hm_greedy_longest.argtypes = [vp, vp, vp, vp]
+    L.hm_pairfreq_create.argtypes = [C.POINTER(vp), C.c_int, i64]
+    L.hm_pairfreq_destroy.argtypes = [vp]
+    L.hm_pairfreq_add.argtypes = [vp, vp, vp, vp, i64, i64, i64, vp]
+    L.hm_pairfreq_read.argtypes = [vp, pi64, pi64, pi64, vp, vp, vp, i64, vp]
     L.hm_comm_unique_id.argtypes = [vp]
     L.hm_comm_init.argtypes = [vp, vp, C.c_int, C.c_int]
     L.hm_comm_destroy.argtypes = [vp]

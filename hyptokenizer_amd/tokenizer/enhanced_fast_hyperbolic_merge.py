@@ -16,6 +16,8 @@ What runs where
   ~2.5 ms per candidate here (50 ``distance().item()`` calls); a refresh scores EVERY candidate.
 * **GPU (``hm_project_table``)** -- ``_project_embeddings`` (``:784-792``) over the whole table in
   place, scan images and norm bounds rebuilt in the same pass.
+* **GPU (``hm_tokenize_batch`` + ``hm_pairfreq_add``)** -- the corpus pass of ``_compute_pair_frequencies``
+  (``:266-289``): the adjacent-pair histogram of the tokenised corpus, in the dict's insertion order (pair_counter.py).
 * **GPU (``hm_greedy_count``)** -- the greedy longest-match counts behind the compression term (``:813-899``): all
   cache entries a batch of candidates is missing, in one call (``greedy_matcher.GreedyMatcher``).
 * **host Python, reference order kept** -- everything that consumes an RNG or touches strings:
@@ -49,6 +51,7 @@ from tqdm import tqdm
 
 from .fast_hyperbolic_merge import CandidateList, FastHyperbolicTokenizer, MergeCandidate
 from .hyperbolic_merge import TQDM_OFF, _loop_without_cyclic_gc
+from .pair_counter import count_lines_device, read_corpus_lines, tokenize_customised
 
 try:  # the reference consults WordNet when nltk is installed (:39-47); it is optional here too
     import nltk  # noqa: F401
@@ -160,6 +163,43 @@ def _row_means(dist: np.ndarray, keep: np.ndarray) -> np.ndarray:
         vals = d64[r][keep[r]]
         out[r] = np.mean(vals) if vals.size else np.nan       # empty: the caller returns 0.0 (:335-336)
     return out
+
+
+def coherence_batch(eng, ii: np.ndarray, jj: np.ndarray, w: np.ndarray, draw, c: float, merge_threshold: float,
+                    shard=None) -> np.ndarray:
+    """``1 / (1 + exp(mean distance - merge_threshold))`` of every candidate's simulated merged embedding
+    ``exp_map(x_i, w * log_map(x_i, x_j))`` to its sampled rows, 0.0 when no sample is kept (the reference's
+    ``_compute_semantic_coherence`` of the enhanced class ``:291-346`` and of FrequencyAwareHyperbolicTokenizer
+    ``:114-166``, which are the same arithmetic).  ``draw(k)`` returns the next ``k`` candidates' samples (one
+    ``torch.randperm(n)[:50]`` each): the RNG calls happen in list order; midpoints and all ``count x 50`` distances
+    are ONE kernel launch (two when the list is long: the second half's samples are drawn while the first half runs);
+    mean / sigmoid in float64 as ``np.mean`` / ``np.exp`` give them."""
+    count = len(ii)
+    if count == 0:
+        return np.zeros(0, np.float64)
+    if shard is not None:
+        from ..sharding import sharded_coherence
+        samples = draw(count)          # (every rank draws the same samples: same seeded generator)
+        dist = sharded_coherence(eng, shard, ii, jj, w.astype(np.float32), samples, c)
+    elif count >= 64 and hasattr(eng, "coherence_distances_begin"):
+        # two halves, samples drawn in candidate order as ever: while the first half's kernel and result copy run, the
+        # host draws the second half's permutations (the long pole: one MT19937 pass over n draws per candidate)
+        h = count // 2
+        s0 = draw(h)
+        pend = eng.coherence_distances_begin(ii[:h], jj[:h], w[:h].astype(np.float32), s0, c)
+        s1 = draw(count - h)
+        d1 = eng.coherence_distances(ii[h:], jj[h:], w[h:].astype(np.float32), s1, c)
+        samples = np.concatenate([s0, s1])
+        dist = np.concatenate([eng.coherence_distances_end(pend), d1])
+    else:
+        samples = draw(count)
+        dist = eng.coherence_distances(ii, jj, w.astype(np.float32), samples, c)
+    keep = (samples != ii[:, None]) & (samples != jj[:, None])
+    avg = _row_means(dist, keep)
+    with np.errstate(over="ignore", invalid="ignore"):
+        coh = 1.0 / (1.0 + np.exp(avg - merge_threshold))
+    coh[~keep.any(axis=1)] = 0.0
+    return coh
 
 
 class EnhancedFastHyperbolicTokenizer(FastHyperbolicTokenizer):
@@ -275,13 +315,17 @@ class EnhancedFastHyperbolicTokenizer(FastHyperbolicTokenizer):
         if not self.use_frequency_aware:
             return
         logger.info("Computing pair frequencies from corpus...")
-        seen = 0
-        with open(corpus_path, "r", encoding="utf-8") as f:
-            for line in tqdm(f, desc="Computing frequencies", disable=TQDM_OFF):
-                toks = self.tokenize(line.strip())
-                for pair in zip(toks, toks[1:]):
-                    self.pair_frequencies[pair] = self.pair_frequencies.get(pair, 0) + 1
-                    seen += 1
+        if self.device.type == "cuda" and not tokenize_customised(self):
+            # hm_tokenize_batch + hm_pairfreq_add over slabs of lines: the same dict, in the same order (pair_counter.py)
+            seen = count_lines_device(self, read_corpus_lines(corpus_path), self.pair_frequencies)
+        else:
+            seen = 0
+            with open(corpus_path, "r", encoding="utf-8") as f:
+                for line in tqdm(f, desc="Computing frequencies", disable=TQDM_OFF):
+                    toks = self.tokenize(line.strip())
+                    for pair in zip(toks, toks[1:]):
+                        self.pair_frequencies[pair] = self.pair_frequencies.get(pair, 0) + 1
+                        seen += 1
         logger.info(f"Computed frequencies for {len(self.pair_frequencies)} unique token pairs "
                     f"from {seen} total pairs")
 
@@ -315,39 +359,15 @@ class EnhancedFastHyperbolicTokenizer(FastHyperbolicTokenizer):
         return randperm_prefixes(n, min(COHERENCE_SAMPLES, n), count)
 
     def _semantic_coherence_batch(self, ii: np.ndarray, jj: np.ndarray) -> np.ndarray:
-        """Reference ``_compute_semantic_coherence`` (``:291-346``) for a list of candidates: the RNG
-        calls happen first, in list order; midpoints and all ``count x 50`` distances are ONE kernel
-        launch; mean / sigmoid in float64 as ``np.mean`` / ``np.exp`` give them."""
+        """Reference ``_compute_semantic_coherence`` (``:291-346``) for a list of candidates (``coherence_batch``)."""
         count = len(ii)
         if not self.use_frequency_aware or count == 0:
             return np.zeros(count, np.float64)
         lens = self._token_lengths()                      # len(vocab[r]), kept as an array and extended as tokens are appended
         li, lj = lens[ii], lens[jj]
         w = (lj / (li + lj)).astype(np.float64)           # weight_j, a Python double in the reference (:316)
-        eng = self._get_engine()
-        if self.shard is not None:
-            from ..sharding import sharded_coherence
-            samples = self._coherence_samples(count)          # (every rank draws the same samples: same seeded generator)
-            dist = sharded_coherence(eng, self.shard, ii, jj, w.astype(np.float32), samples, self._c())
-        elif count >= 64 and hasattr(eng, "coherence_distances_begin"):
-            # two halves, samples drawn in candidate order as ever: while the first half's kernel and result copy run, the
-            # host draws the second half's permutations (the long pole: one MT19937 pass over n draws per candidate)
-            h = count // 2
-            s0 = self._coherence_samples(h)
-            pend = eng.coherence_distances_begin(ii[:h], jj[:h], w[:h].astype(np.float32), s0, self._c())
-            s1 = self._coherence_samples(count - h)
-            d1 = eng.coherence_distances(ii[h:], jj[h:], w[h:].astype(np.float32), s1, self._c())
-            samples = np.concatenate([s0, s1])
-            dist = np.concatenate([eng.coherence_distances_end(pend), d1])
-        else:
-            samples = self._coherence_samples(count)
-            dist = eng.coherence_distances(ii, jj, w.astype(np.float32), samples, self._c())
-        keep = (samples != ii[:, None]) & (samples != jj[:, None])
-        avg = _row_means(dist, keep)
-        with np.errstate(over="ignore", invalid="ignore"):
-            coh = 1.0 / (1.0 + np.exp(avg - self.merge_threshold))
-        coh[~keep.any(axis=1)] = 0.0
-        return coh
+        return coherence_batch(self._get_engine(), ii, jj, w, self._coherence_samples, self._c(), self.merge_threshold,
+                               self.shard)
 
     def _compute_semantic_coherence(self, i: int, j: int) -> float:
         return float(self._semantic_coherence_batch(np.array([i], np.int32), np.array([j], np.int32))[0])

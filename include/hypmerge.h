@@ -357,6 +357,31 @@ int hm_last_scan_stats(const hm_engine* e, float* scan_ms, int64_t* pairs, int64
  * covered and number of launches.  reset != 0 clears the totals after reading. */
 int hm_scan_totals(hm_engine* e, double* scan_ms, int64_t* pairs, int64_t* launches, int reset);
 
+/* ---- adjacent-pair histogram of a tokenised corpus (frequency-aware scoring) --------------------------------
+ * Exact counts of the adjacent symbol pairs of a corpus, streamed in slabs of lines, with the smallest flat position
+ * of every pair (sorting by it gives the order in which the reference's dict first meets the pairs).  Symbols are
+ * those of hm_tokenize_batch: in [-(2 + 0x10FFFF), 2^21).  A pair key is ((a + 0x110001) << 22) | (b + 0x110001).
+ * Independent of any engine; errors are reported through hm_last_error(NULL).  Every entry point synchronises
+ * `stream` before it returns.
+ *
+ * hm_pairfreq_create / hm_pairfreq_destroy: one counter on device `device`.  initial_capacity (0: 65 536) sizes the
+ * first hash tables; a small value is a test hook (the tables grow, and a slab that overflows its table is recounted).
+ * Replaces: the dict self.pair_frequencies being filled (frequency_aware_hyperbolic_merge.py:92-112). */
+typedef struct hm_pairfreq hm_pairfreq;
+int hm_pairfreq_create(hm_pairfreq** out, int device, int64_t initial_capacity);
+int hm_pairfreq_destroy(hm_pairfreq* pf);
+/* One slab, DEVICE arrays: line l holds sym_dev[offsets_dev[l] .. offsets_dev[l] + len_dev[l]) (len_dev NULL: up to
+ * offsets_dev[l + 1]; offsets_dev[0] = 0, n_positions = offsets_dev[n_lines]).  Adds every pair whose two positions lie
+ * in one line, at flat position base + p.  LIMITS (HM_E_ARG): n_positions < 2^40, base + n_positions <= 2^62.
+ * Replaces: for line in f: tokens = self.tokenize(line.strip()); for pair in zip(tokens, tokens[1:]): ... += 1. */
+int hm_pairfreq_add(hm_pairfreq* pf, const int32_t* sym_dev, const int64_t* offsets_dev, const int32_t* len_dev,
+                    int64_t n_lines, int64_t n_positions, int64_t base, void* stream);
+/* Distinct pairs, total pairs and slab recounts so far (any pointer may be NULL); with the three device arrays (room for
+ * out_cap >= n_distinct entries, HM_E_CAPACITY otherwise) also every distinct pair's key, count and first position, in
+ * no particular order. */
+int hm_pairfreq_read(hm_pairfreq* pf, int64_t* n_distinct, int64_t* n_pairs, int64_t* slab_recounts, uint64_t* keys_dev,
+                     uint64_t* counts_dev, int64_t* first_dev, int64_t out_cap, void* stream);
+
 /* Test hook: pretend the previous refresh ended on this emission cut (bits of u'); the next whole-table top-k
  * search starts from it as given and has to notice by itself when it is too tight. */
 int hm_debug_force_cut(hm_engine* e, uint32_t cut_bits, int64_t k, float c);
