@@ -24,6 +24,8 @@ COMM_ID_BYTES = 128
 SIGN_REFERENCE, SIGN_LORENTZ = 0, 1
 PREFILTER_AUTO, PREFILTER_F32, PREFILTER_BF16 = 0, 1, 2
 LOOP_MAX_STEPS = 256
+NGRAM_WEIGHTED, NGRAM_DISTINCT = 0, 1
+CM_CODES, CM_CLASSES, CM_SLOTS = 10, 55, 57
 
 #: every symbol include/hypmerge.h declares (tests check that the library exports all of them)
 EXPORTED_SYMBOLS = (
@@ -39,6 +41,8 @@ EXPORTED_SYMBOLS = (
     "hm_comm_unique_id", "hm_comm_init", "hm_comm_destroy", "hm_comm_info", "hm_shard_merge_steps", "hm_global_argmin", "hm_global_topk",
     "hm_greedy_create", "hm_greedy_destroy", "hm_greedy_set_corpus", "hm_greedy_add_strings", "hm_greedy_count",
     "hm_greedy_longest", "hm_pairfreq_create", "hm_pairfreq_destroy", "hm_pairfreq_add", "hm_pairfreq_read",
+    "hm_ngram_create", "hm_ngram_destroy", "hm_ngram_count", "hm_ngram_read", "hm_classmin_create", "hm_classmin_destroy",
+    "hm_classmin_set_codes", "hm_classmin_build", "hm_classmin_fold",
 )
 
 
@@ -112,6 +116,15 @@ def load() -> C.CDLL:
     L.hm_pairfreq_destroy.argtypes = [vp]
     L.hm_pairfreq_add.argtypes = [vp, vp, vp, vp, i64, i64, i64, vp]
     L.hm_pairfreq_read.argtypes = [vp, pi64, pi64, pi64, vp, vp, vp, i64, vp]
+    L.hm_ngram_create.argtypes = [C.POINTER(vp), C.c_int, i64]
+    L.hm_ngram_destroy.argtypes = [vp]
+    L.hm_ngram_count.argtypes = [vp, vp, vp, vp, i64, C.c_int, pi64, vp]
+    L.hm_ngram_read.argtypes = [vp, vp, vp, vp, i64, pi64, vp]
+    L.hm_classmin_create.argtypes = [C.POINTER(vp), vp]
+    L.hm_classmin_destroy.argtypes = [vp]
+    L.hm_classmin_set_codes.argtypes = [vp, vp, i64, i64, vp]
+    L.hm_classmin_build.argtypes = [vp, f32, vp, vp]
+    L.hm_classmin_fold.argtypes = [vp, i64, f32, vp, i64, vp, vp]
     L.hm_comm_unique_id.argtypes = [vp]
     L.hm_comm_init.argtypes = [vp, vp, C.c_int, C.c_int]
     L.hm_comm_destroy.argtypes = [vp]

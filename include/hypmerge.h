@@ -382,6 +382,53 @@ int hm_pairfreq_add(hm_pairfreq* pf, const int32_t* sym_dev, const int64_t* offs
 int hm_pairfreq_read(hm_pairfreq* pf, int64_t* n_distinct, int64_t* n_pairs, int64_t* slab_recounts, uint64_t* keys_dev,
                      uint64_t* counts_dev, int64_t* first_dev, int64_t out_cap, void* stream);
 
+/* ---- character n-gram histogram of a word list (hierarchical tokenizer statistics) --------------------------------
+ * Exact counts of every n-gram of length 2..5 of a list of words given as code points (any value: the n-grams are
+ * compared code point by code point).  HOST arrays: word w is cps[offsets[w] .. offsets[w + 1]) (offsets[0] = 0,
+ * non-decreasing, total below 2^40, fewer than 2^32 words).
+ *   HM_NGRAM_WEIGHTED: count(g) = sum over the occurrences of g of weights[w] (int64 >= 0)
+ *   HM_NGRAM_DISTINCT: count(g) = number of words that contain g (weights ignored, may be NULL)
+ * Independent of any engine; errors are reported through hm_last_error(NULL).  Every entry point synchronises `stream`.
+ * initial_capacity (0: 65 536) sizes the first hash table; a small value is a test hook (an overflowing count is redone
+ * into larger tables).
+ * Replaces: for word in words: for n in range(2, min(6, len(word) + 1)): ... subword_counter[word[i:i+n]] += 1
+ * (hierarchical_hyperbolic_merge.py:110-156) and sum(1 for word in self.common_words if token in word) (:193-198). */
+#define HM_NGRAM_WEIGHTED 0
+#define HM_NGRAM_DISTINCT 1
+typedef struct hm_ngram hm_ngram;
+int hm_ngram_create(hm_ngram** out, int device, int64_t initial_capacity);
+int hm_ngram_destroy(hm_ngram* g);
+/* Counts the words; *n_distinct (may be NULL) = distinct n-grams.  Replaces the result of an earlier count. */
+int hm_ngram_count(hm_ngram* g, const int32_t* cps, const int64_t* offsets, const int64_t* weights, int64_t n_words, int mode,
+                   int64_t* n_distinct, void* stream);
+/* The last count's n-grams into HOST arrays (room for out_cap >= n_distinct, HM_E_CAPACITY otherwise; all three or none):
+ * n-gram k is cps[pos[k] .. pos[k] + len[k]) of the last count's input, with its count; no particular order.
+ * *recounts (may be NULL): counts redone into larger tables since creation. */
+int hm_ngram_read(hm_ngram* g, int64_t* pos, int32_t* len, int64_t* counts, int64_t out_cap, int64_t* recounts, void* stream);
+
+/* ---- per-class running minima of the pair distance (hierarchical tokenizer step selection) -------------------------
+ * Every live row carries a code in [0, HM_CM_CODES); a pair i < j belongs to the class of its unordered code pair,
+ * cls(a, b) = lo * HM_CM_CODES - lo * (lo - 1) / 2 + (hi - lo) with lo = min(a, b), hi = max(a, b).  A record is
+ * uint32[4] {found, bits(d), i, j}: the lexicographic minimum of (bits(d), i, j) over the class's pairs, d the engine's
+ * canonical distance (the one hm_pairwise_candidates lists), NaN excluded, NO threshold.  found = 0: the class is empty.
+ * One handle per engine, on the engine's device; errors through hm_last_error(engine).  Every entry point synchronises.
+ * Replaces: min over the candidate list of hierarchical_hyperbolic_merge.py:279-428, filtered per phase. */
+#define HM_CM_CODES 10
+#define HM_CM_CLASSES 55
+#define HM_CM_SLOTS 57
+typedef struct hm_classmin hm_classmin;
+int hm_classmin_create(hm_classmin** out, hm_engine* e);
+int hm_classmin_destroy(hm_classmin* cm);
+/* HOST codes[r - row_begin] of rows [row_begin, row_end) (each < HM_CM_CODES). */
+int hm_classmin_set_codes(hm_classmin* cm, const uint8_t* codes, int64_t row_begin, int64_t row_end, void* stream);
+/* One exact pass over every pair of the live rows: out[4 * q ..] = record of class q, q < HM_CM_CLASSES (HOST). */
+int hm_classmin_build(hm_classmin* cm, float c, uint32_t* out, void* stream);
+/* Row `row` against rows [0, row): out[4 * q ..] (q < HM_CM_CLASSES) = record of class q over the pairs (i, row); and over the
+ * HOST list partners[] (index | 1 << 28: exception list A, | 1 << 29: exception list B; every index below `row`):
+ * out[4 * HM_CM_CLASSES ..] = record of the A pairs, out[4 * (HM_CM_CLASSES + 1) ..] = record of the B pairs. */
+int hm_classmin_fold(hm_classmin* cm, int64_t row, float c, const int32_t* partners, int64_t n_partners, uint32_t* out,
+                     void* stream);
+
 /* Test hook: pretend the previous refresh ended on this emission cut (bits of u'); the next whole-table top-k
  * search starts from it as given and has to notice by itself when it is too tight. */
 int hm_debug_force_cut(hm_engine* e, uint32_t cut_bits, int64_t k, float c);
