@@ -43,6 +43,8 @@ EXPORTED_SYMBOLS = (
     "hm_greedy_longest", "hm_pairfreq_create", "hm_pairfreq_destroy", "hm_pairfreq_add", "hm_pairfreq_read",
     "hm_ngram_create", "hm_ngram_destroy", "hm_ngram_count", "hm_ngram_read", "hm_classmin_create", "hm_classmin_destroy",
     "hm_classmin_set_codes", "hm_classmin_build", "hm_classmin_fold",
+    "hm_rows_minkowski_bwd", "hm_rows_distance_bwd", "hm_rows_log_map_bwd", "hm_rows_exp_map_bwd", "hm_rows_project_bwd",
+    "hm_batch_distance_bwd", "hm_infonce_fwd", "hm_infonce_bwd", "hm_triplet_fwd_bwd",
 )
 
 
@@ -154,6 +156,15 @@ def load() -> C.CDLL:
     L.hm_rows_log_map.argtypes = [vp, vp, i64, i64, C.c_int, C.c_int, vp, i64, vp]
     L.hm_rows_exp_map.argtypes = [vp, vp, i64, i64, C.c_int, vp, i64, vp]
     L.hm_rows_project.argtypes = [vp, i64, i64, C.c_int, f32, vp, i64, vp]
+    L.hm_rows_minkowski_bwd.argtypes = [vp, vp, vp, i64, i64, C.c_int, C.c_int, vp, vp, i64, vp]
+    L.hm_rows_distance_bwd.argtypes = [vp, vp, vp, i64, i64, C.c_int, f32, C.c_int, vp, vp, i64, vp]
+    L.hm_rows_log_map_bwd.argtypes = [vp, vp, vp, i64, i64, i64, C.c_int, C.c_int, vp, vp, i64, vp]
+    L.hm_rows_exp_map_bwd.argtypes = [vp, vp, vp, i64, i64, i64, C.c_int, vp, vp, i64, vp]
+    L.hm_rows_project_bwd.argtypes = [vp, vp, i64, i64, i64, C.c_int, f32, vp, i64, vp]
+    L.hm_batch_distance_bwd.argtypes = [vp, i64, vp, i64, i64, i64, C.c_int, f32, C.c_int, vp, i64, vp, vp, i64, vp]
+    L.hm_infonce_fwd.argtypes = [vp, vp, i64, i64, i64, C.c_int, f32, C.c_int, vp, vp, vp, vp, vp, vp]
+    L.hm_infonce_bwd.argtypes = [vp, vp, i64, i64, i64, C.c_int, f32, C.c_int, vp, vp, vp, vp, vp, i64, vp]
+    L.hm_triplet_fwd_bwd.argtypes = [vp, vp, vp, i64, i64, C.c_int, f32, C.c_int, vp, vp, vp, vp, vp, i64, vp]
     L.hm_last_scan_stats.argtypes = [vp, pf32, pi64, pi64, pi32]
     L.hm_scan_totals.argtypes = [vp, C.POINTER(C.c_double), pi64, pi64, C.c_int]
     for name in EXPORTED_SYMBOLS:

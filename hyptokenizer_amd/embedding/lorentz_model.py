@@ -12,6 +12,11 @@ Sign convention: the reference's ``minkowski_dot`` is ``x0*y0 
 default ``"reference"`` reproduces exactly that; ``"lorentz"`` flips the sign of the form (the
 behaviour the reference's own ``test_distance`` expects).  Every function takes an optional
 ``sign_convention=`` keyword; ``set_sign_convention`` changes the default.
+
+Autograd: when gradients are being recorded and an operand requires grad, the hot-path functions run as
+``torch.autograd.Function``s of ``_autograd.py`` (same forward entry points, HIP backward kernels), so they are
+differentiable like the reference's torch expressions; every other call takes the plain path.  The helpers built on
+``minkowski_dot`` inherit that.  ``c`` is a Python float (no gradient); second derivatives raise ``RuntimeError``.
 """
 from __future__ import annotations
 
@@ -20,6 +25,7 @@ from typing import Optional
 import torch
 
 from ..engine import device_batch_distance, device_rows_op, sign_mode_id
+from . import _autograd as _ag
 
 _DEFAULT_SIGN = "reference"
 
@@ -41,6 +47,8 @@ def _sign(sign_convention) -> int:
 
 def minkowski_dot(x: torch.Tensor, y: torch.Tensor, *, sign_convention: Optional[str] = None) -> torch.Tensor:
     """Reference ``lorentz_model.py:14-25``: ``x0*y0 - sum_k xk*yk`` (negated under "lorentz")."""
+    if _ag.wants_grad(x, y):
+        return _ag.pair_op("minkowski", x, y, 1.0, _sign(sign_convention))
     return device_rows_op("minkowski", x, y, 1.0, _sign(sign_convention))
 
 
@@ -51,6 +59,8 @@ def minkowski_norm(x: torch.Tensor, *, sign_convention: Optional[str] = None) ->
 
 def project_to_hyperboloid(x: torch.Tensor, c: float = 1.0) -> torch.Tensor:
     """Reference ``:41-56``: keep the spatial part, ``x0 = sqrt(1 + c*||x_1:||^2)``."""
+    if _ag.wants_grad(x):
+        return _ag.project(x, float(c))
     return device_rows_op("project", x, None, float(c), 0)
 
 
@@ -61,28 +71,38 @@ def lorentz_to_klein(x: torch.Tensor, c: float = 1.0) -> torch.Tensor:
 
 def exp_map(x: torch.Tensor, v: torch.Tensor, c: float = 1.0) -> torch.Tensor:
     """Reference ``:73-93``: Euclidean norm of the spatial part of v, ``cosh(n) x + sinh(n) v/n``."""
+    if _ag.wants_grad(x, v):
+        return _ag.pair_op("exp_map", x, v, 1.0, 0)
     return device_rows_op("exp_map", x, v, 1.0, 0)
 
 
 def log_map(x: torch.Tensor, y: torch.Tensor, c: float = 1.0, *, sign_convention: Optional[str] = None) -> torch.Tensor:
     """Reference ``:96-119`` (the curvature argument is ignored there as well)."""
+    if _ag.wants_grad(x, y):
+        return _ag.pair_op("log_map", x, y, 1.0, _sign(sign_convention))
     return device_rows_op("log_map", x, y, 1.0, _sign(sign_convention))
 
 
 def distance(x: torch.Tensor, y: torch.Tensor, c: float = 1.0, *, sign_convention: Optional[str] = None) -> torch.Tensor:
     """Reference ``:122-138``: ``acosh(clamp(u, 1)) / sqrt(c)`` on broadcast operands."""
+    if _ag.wants_grad(x, y):
+        return _ag.pair_op("distance", x, y, float(c), _sign(sign_convention))
     return device_rows_op("distance", x, y, float(c), _sign(sign_convention))
 
 
 def batch_distance(x: torch.Tensor, y: torch.Tensor, c: float = 1.0, *,
                    sign_convention: Optional[str] = None) -> torch.Tensor:
     """Reference ``:141-178``: all-pairs distances ``[B1, B2]`` without the ``(B1, B2, d+1)`` temporary."""
+    if _ag.wants_grad(x, y):
+        return _ag.batch_distance(x, y, float(c), _sign(sign_convention))
     return device_batch_distance(x, y, float(c), _sign(sign_convention))
 
 
 def batch_distance_optimized(x: torch.Tensor, y: torch.Tensor, c: float = 1.0, *,
                              sign_convention: Optional[str] = None) -> torch.Tensor:
     """Reference ``:181-210`` (einsum form; same values as ``batch_distance`` here)."""
+    if _ag.wants_grad(x, y):
+        return _ag.batch_distance(x, y, float(c), _sign(sign_convention))
     return device_batch_distance(x, y, float(c), _sign(sign_convention))
 
 

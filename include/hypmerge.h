@@ -347,6 +347,50 @@ int hm_rows_exp_map(const float* x_dev, const float* v_dev, int64_t b, int64_t l
 int hm_rows_project(const float* x_dev, int64_t b, int64_t ld, int d1, float c, float* out_dev,
                     int64_t ld_out, void* stream);
 
+/* Vector-Jacobian products of the row-wise primitives above (upstream gradient g, same row layout; outputs [b, d1] with
+ * leading dimension ld_out).  The derivative is that of the reference's torch expression as torch differentiates it:
+ * clamp(u, min = 1 + 1e-8) passes the gradient where u >= 1.0f and gives exactly 0 below; acosh' = 1 / sqrt(a^2 - 1) is
+ * +-inf at a == 1; the mask arithmetic of log_map / exp_map is walked back term by term.  No gradient with respect to c.
+ *   hm_rows_minkowski_bwd : g[b]            -> gx, gy     (:14-25)
+ *   hm_rows_distance_bwd  : g[b]            -> gx, gy     (:122-138)
+ *   hm_rows_log_map_bwd   : g[b, d1] (ld_g) -> gx, gy     (:96-119)
+ *   hm_rows_exp_map_bwd   : g[b, d1] (ld_g) -> gx, gv     (:73-93)
+ *   hm_rows_project_bwd   : g[b, d1] (ld_g) -> gx         (:41-56; column 0 of gx is 0)
+ *   hm_batch_distance_bwd : G[n1, n2] (ld_g) -> gX[n1, d1], gY[n2, d1] (:141-210; either output may be NULL); every row
+ *                           is summed over the other table's rows in ascending order, no atomics: same bits on every run */
+int hm_rows_minkowski_bwd(const float* x_dev, const float* y_dev, const float* g_dev, int64_t b, int64_t ld, int d1,
+                          int sign_mode, float* gx_dev, float* gy_dev, int64_t ld_out, void* stream);
+int hm_rows_distance_bwd(const float* x_dev, const float* y_dev, const float* g_dev, int64_t b, int64_t ld, int d1,
+                         float c, int sign_mode, float* gx_dev, float* gy_dev, int64_t ld_out, void* stream);
+int hm_rows_log_map_bwd(const float* x_dev, const float* y_dev, const float* g_dev, int64_t ld_g, int64_t b, int64_t ld,
+                        int d1, int sign_mode, float* gx_dev, float* gy_dev, int64_t ld_out, void* stream);
+int hm_rows_exp_map_bwd(const float* x_dev, const float* v_dev, const float* g_dev, int64_t ld_g, int64_t b, int64_t ld,
+                        int d1, float* gx_dev, float* gv_dev, int64_t ld_out, void* stream);
+int hm_rows_project_bwd(const float* x_dev, const float* g_dev, int64_t ld_g, int64_t b, int64_t ld, int d1, float c,
+                        float* gx_dev, int64_t ld_out, void* stream);
+int hm_batch_distance_bwd(const float* X_dev, int64_t n1, const float* Y_dev, int64_t n2, int64_t ld_x, int64_t ld_y,
+                          int d1, float c, int sign_mode, const float* G_dev, int64_t ld_g, float* gX_dev, float* gY_dev,
+                          int64_t ld_out, void* stream);
+
+/* Fused hyperbolic InfoNCE (multimodal/contrastive_loss.py:17-61 of the reference, c = 1): S = -distance / temp between
+ * z_text[n, d1] and z_img[n, d1], cross-entropy over rows and over columns against the diagonal, averaged.  The n x n
+ * matrix is never stored.  n <= 65536, d1 <= 129.
+ *   hm_infonce_fwd : lse_row[n], lse_col[n] (log-sum-exp of the rows / columns of S), diag[n] = S_ii,
+ *                    losses[n] = ((lse_row - diag) + (lse_col - diag)) / 2 and *total = their sum in a fixed order
+ *   hm_infonce_bwd : gradients of sum_i w[i] * losses[i] with respect to z_text and z_img (either output may be NULL),
+ *                    from the two log-sum-exp vectors of the forward call; fixed summation order, no atomics */
+int hm_infonce_fwd(const float* zt_dev, const float* zi_dev, int64_t n, int64_t ld_t, int64_t ld_i, int d1, float temp,
+                   int sign_mode, float* lse_row_dev, float* lse_col_dev, float* diag_dev, float* losses_dev,
+                   float* total_dev, void* stream);
+int hm_infonce_bwd(const float* zt_dev, const float* zi_dev, int64_t n, int64_t ld_t, int64_t ld_i, int d1, float temp,
+                   int sign_mode, const float* lse_row_dev, const float* lse_col_dev, const float* w_dev,
+                   float* g_text_dev, float* g_img_dev, int64_t ld_out, void* stream);
+/* Triplet loss (:64-97, c = 1): losses[b] = relu(d(a, p) - d(a, n) + margin) (losses_dev may be NULL); with w_dev the
+ * gradients of sum_t w[t] * losses[t] as well (relu' at exactly 0 is 0), without w_dev the forward values alone. */
+int hm_triplet_fwd_bwd(const float* a_dev, const float* p_dev, const float* n_dev, int64_t b, int64_t ld, int d1,
+                       float margin, int sign_mode, const float* w_dev, float* losses_dev, float* ga_dev, float* gp_dev,
+                       float* gn_dev, int64_t ld_out, void* stream);
+
 /* Timing of the last scan launched by hm_pairwise_argmin / hm_pairwise_topk on this engine,
  * measured with HIP events on the stream the kernel ran on (bench.py roofline).
  * *scan_ms = duration of the dominant pair-scan kernel launch(es); *pairs = pairs it covered. */
