@@ -45,6 +45,7 @@ EXPORTED_SYMBOLS = (
     "hm_classmin_set_codes", "hm_classmin_build", "hm_classmin_fold",
     "hm_rows_minkowski_bwd", "hm_rows_distance_bwd", "hm_rows_log_map_bwd", "hm_rows_exp_map_bwd", "hm_rows_project_bwd",
     "hm_batch_distance_bwd", "hm_infonce_fwd", "hm_infonce_bwd", "hm_triplet_fwd_bwd",
+    "hm_retrieval_ranks", "hm_knn", "hm_debug_retrieval_layout",
 )
 
 
@@ -165,6 +166,9 @@ def load() -> C.CDLL:
     L.hm_infonce_fwd.argtypes = [vp, vp, i64, i64, i64, C.c_int, f32, C.c_int, vp, vp, vp, vp, vp, vp]
     L.hm_infonce_bwd.argtypes = [vp, vp, i64, i64, i64, C.c_int, f32, C.c_int, vp, vp, vp, vp, vp, i64, vp]
     L.hm_triplet_fwd_bwd.argtypes = [vp, vp, vp, i64, i64, C.c_int, f32, C.c_int, vp, vp, vp, vp, vp, i64, vp]
+    L.hm_retrieval_ranks.argtypes = [vp, vp, i64, i64, i64, C.c_int, C.c_int, vp, vp, vp]
+    L.hm_debug_retrieval_layout.argtypes = [C.c_int]
+    L.hm_knn.argtypes = [vp, i64, vp, i64, i64, i64, C.c_int, f32, C.c_int, C.c_int, C.c_int, vp, vp, vp]
     L.hm_last_scan_stats.argtypes = [vp, pf32, pi64, pi64, pi32]
     L.hm_scan_totals.argtypes = [vp, C.POINTER(C.c_double), pi64, pi64, C.c_int]
     for name in EXPORTED_SYMBOLS:

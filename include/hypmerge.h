@@ -391,6 +391,29 @@ int hm_triplet_fwd_bwd(const float* a_dev, const float* p_dev, const float* n_de
                        float margin, int sign_mode, const float* w_dev, float* losses_dev, float* ga_dev, float* gp_dev,
                        float* gn_dev, int64_t ld_out, void* stream);
 
+/* Fused hyperbolic retrieval: one walk over the pair tiles, the n x n distance matrix is never stored.  With
+ * D[i, j] = distance(z_text[i], z_img[j]) in the canonical fp32 arithmetic (the bits of hm_batch_distance), c = 1:
+ *   rank_t2i[i] = #{ j : D[i, j] < D[i, i] } + #{ j < i : D[i, j] == D[i, i] }
+ *   rank_i2t[j] = #{ i : D[i, j] < D[j, j] } + #{ i < j : D[i, j] == D[j, j] }
+ * NaN orders as torch.sort orders it (greater than every number, equal to NaN).  Pair i is retrieved at k iff its rank < k.
+ * Either output may be NULL.  1 <= n <= 65536, 2 <= d1 <= 129.  No atomics: the same bits on every run.
+ * Replaces compute_recall_at_k of the reference (scripts/train_retrieval.py:176-229, called at :403 and :459): B^2 calls of
+ * distance(...).item() into a matrix, then torch.topk per row and per column. */
+int hm_retrieval_ranks(const float* zt_dev, const float* zi_dev, int64_t n, int64_t ld_t, int64_t ld_i, int d1,
+                       int sign_mode, int32_t* rank_t2i_dev, int32_t* rank_i2t_dev, void* stream);
+/* Exact k nearest keys of every query: d_out[nq, k], i_out[nq, k] = the k smallest (distance, key index) of each row of
+ * hm_batch_distance(q, keys, c), ascending, with the same bits.  NaN distances are never selected; a row with fewer than k
+ * selectable keys is padded with (+inf, -1).  exclude_self != 0 skips key i for query i.  d_out doubles as the call's only
+ * working memory.  1 <= k <= 128, k <= nk, nq and nk <= 2^20, 2 <= d1 <= 129.
+ * Replaces the per-query search of the reference's FAISS branch (index.search(q, k): tokenizer/hyperbolic_merge.py:217,
+ * tokenizer/fast_hyperbolic_merge.py:302-304). */
+int hm_knn(const float* q_dev, int64_t nq, const float* k_dev, int64_t nk, int64_t ld_q, int64_t ld_k, int d1, float c,
+           int sign_mode, int k, int exclude_self, float* d_out_dev, int32_t* i_out_dev, void* stream);
+/* Test / tuning hook (results never depend on it): the tile layout hm_retrieval_ranks launches from now on, process-wide.
+ * 0 = the default (the faster one of the two), 1 = A and B rows in LDS (the layout of 5.11), 2 = A rows in
+ * registers and B rows read as 16-byte LDS broadcasts.  tools/retrieval_probe.py times 1 against 2 in one process. */
+int hm_debug_retrieval_layout(int layout);
+
 /* Timing of the last scan launched by hm_pairwise_argmin / hm_pairwise_topk on this engine,
  * measured with HIP events on the stream the kernel ran on (bench.py roofline).
  * *scan_ms = duration of the dominant pair-scan kernel launch(es); *pairs = pairs it covered. */
