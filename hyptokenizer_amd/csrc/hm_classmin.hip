@@ -15,7 +15,7 @@
 //
 // Rows are only appended and existing distances never change, so the host keeps the running minima: after a merge
 // the minimum of a class is lexmin(previous, fold of the new row).
-#include "hm_common.h"
+#include "hm_table.h"
 #include "hm_rows_device.h"
 
 #pragma clang fp contract(off)
@@ -24,11 +24,10 @@
 
 struct hm_classmin {
     hm_engine* e = nullptr;
-    uint8_t* d_codes = nullptr;                // [max_rows]
-    unsigned long long* d_keys = nullptr;      // [HM_CM_SLOTS] (bits(d) << 32) | partner
-    unsigned long long* h_keys = nullptr;      // pinned mirror
-    int32_t* d_partners = nullptr;             // fold: host-listed partners (index | flags)
-    int64_t partner_cap = 0;
+    DevBuf<uint8_t> d_codes;                   // [max_rows]
+    DevBuf<unsigned long long> d_keys;         // [HM_CM_SLOTS] (bits(d) << 32) | partner
+    DevBuf<unsigned long long, true> h_keys;   // pinned mirror
+    DevBuf<int32_t> d_partners;                // fold: host-listed partners (index | flags)
     int64_t codes_set = 0;                     // rows [0, codes_set) have codes
 };
 
@@ -193,8 +192,8 @@ int hm_cm_row_launch(hm_classmin* cm, int64_t row, int64_t p0, int64_t p1, int64
     const int64_t nt = p1 > p0 ? (p1 + HM_TILE_ROWS - 1) / HM_TILE_ROWS - p0 / HM_TILE_ROWS : 0;
     const int tile_blocks = (int)std::max<int64_t>(1, std::min<int64_t>(nt, 1024));
     const int list_blocks = (int)std::min<int64_t>((n_partners + 63) / 64, 256);
-    hipLaunchKernelGGL(hm_cm_row_kernel, dim3((unsigned)(tile_blocks + list_blocks)), dim3(64), hm_cm_row_lds(e), s, e->img, cm->d_codes,
-                       e->RS, e->d, e->sign_mode, sqrt_c, row, p0, p1, (const int32_t*)cm->d_partners, n_partners, tile_blocks, cm->d_keys);
+    hipLaunchKernelGGL(hm_cm_row_kernel, dim3((unsigned)(tile_blocks + list_blocks)), dim3(64), hm_cm_row_lds(e), s, e->img, cm->d_codes.p,
+                       e->RS, e->d, e->sign_mode, sqrt_c, row, p0, p1, (const int32_t*)cm->d_partners.p, n_partners, tile_blocks, cm->d_keys.p);
     HM_HIP(hipGetLastError());
     return HM_OK;
 }
@@ -207,16 +206,12 @@ extern "C" int hm_classmin_create(hm_classmin** out, hm_engine* e)
     *out = nullptr;
     if (!e) return hm_fail(nullptr, HM_E_ARG, "hm_classmin_create: engine is NULL");
     HM_HIP(hipSetDevice(e->device));
-    hm_classmin* cm = new hm_classmin();
+    std::unique_ptr<hm_classmin> cm(new hm_classmin());
     cm->e = e;
-    if (hipMalloc(&cm->d_codes, (size_t)e->max_rows) != hipSuccess
-        || hipMalloc(&cm->d_keys, sizeof(unsigned long long) * HM_CM_SLOTS) != hipSuccess
-        || hipHostMalloc(&cm->h_keys, sizeof(unsigned long long) * HM_CM_SLOTS, hipHostMallocDefault) != hipSuccess
-        || hipMemset(cm->d_codes, 0, (size_t)e->max_rows) != hipSuccess) {
-        hm_classmin_destroy(cm);
+    if (cm->d_codes.alloc(e->max_rows) != hipSuccess || cm->d_keys.alloc(HM_CM_SLOTS) != hipSuccess
+        || cm->h_keys.alloc(HM_CM_SLOTS) != hipSuccess || hipMemset(cm->d_codes.p, 0, (size_t)e->max_rows) != hipSuccess)
         return hm_fail(nullptr, HM_E_NOMEM, "hm_classmin_create: allocation failed");
-    }
-    *out = cm;
+    *out = cm.release();
     return HM_OK;
 }
 
@@ -224,10 +219,6 @@ extern "C" int hm_classmin_destroy(hm_classmin* cm)
 {
     if (!cm) return HM_OK;
     if (cm->e) (void)hipSetDevice(cm->e->device);   // every entry point synchronises its stream: nothing is in flight
-    if (cm->d_codes) (void)hipFree(cm->d_codes);
-    if (cm->d_keys) (void)hipFree(cm->d_keys);
-    if (cm->d_partners) (void)hipFree(cm->d_partners);
-    if (cm->h_keys) (void)hipHostFree(cm->h_keys);
     delete cm;
     return HM_OK;
 }
@@ -243,7 +234,7 @@ extern "C" int hm_classmin_set_codes(hm_classmin* cm, const uint8_t* codes, int6
     if (row_end == row_begin) return HM_OK;
     HM_HIP(hipSetDevice(e->device));
     hipStream_t s = (hipStream_t)stream;
-    HM_HIP(hipMemcpyAsync(cm->d_codes + row_begin, codes, (size_t)(row_end - row_begin), hipMemcpyHostToDevice, s));
+    HM_HIP(hipMemcpyAsync(cm->d_codes.p + row_begin, codes, (size_t)(row_end - row_begin), hipMemcpyHostToDevice, s));
     HM_HIP(hipStreamSynchronize(s));       // `codes` is pageable caller memory
     if (row_begin <= cm->codes_set) cm->codes_set = std::max(cm->codes_set, row_end);
     return HM_OK;
@@ -260,11 +251,11 @@ extern "C" int hm_classmin_build(hm_classmin* cm, float c, uint32_t* out, void* 
     hipStream_t s = (hipStream_t)stream;
     const float sqrt_c = sqrtf(c);
     const int n = (int)e->n;
-    HM_HIP(hipMemsetAsync(cm->d_keys, 0xff, sizeof(unsigned long long) * HM_CM_SLOTS, s));
+    HM_HIP(hipMemsetAsync(cm->d_keys.p, 0xff, sizeof(unsigned long long) * HM_CM_SLOTS, s));
     if (n >= 2) {
         BuildArgs a;
-        a.img = e->img; a.codes = cm->d_codes; a.RS = e->RS; a.d = e->d; a.sign_mode = e->sign_mode; a.sqrt_c = sqrt_c; a.n = n;
-        a.ntj = (n + HM_TILE_ROWS - 1) / HM_TILE_ROWS; a.keys = cm->d_keys;
+        a.img = e->img; a.codes = cm->d_codes.p; a.RS = e->RS; a.d = e->d; a.sign_mode = e->sign_mode; a.sqrt_c = sqrt_c; a.n = n;
+        a.ntj = (n + HM_TILE_ROWS - 1) / HM_TILE_ROWS; a.keys = cm->d_keys.p;
         const size_t lds = sizeof(float) * (size_t)(1 + HM_CM_WAVES) * HM_TILE_ROWS * e->RS;
         for (int t0 = 0; t0 < a.ntj; t0 += 32768) {
             const int nt = std::min(32768, a.ntj - t0);
@@ -274,10 +265,10 @@ extern "C" int hm_classmin_build(hm_classmin* cm, float c, uint32_t* out, void* 
             HM_HIP(hipGetLastError());
         }
     }
-    HM_HIP(hipMemcpyAsync(cm->h_keys, cm->d_keys, sizeof(unsigned long long) * HM_CM_CLASSES, hipMemcpyDeviceToHost, s));
+    HM_HIP(hipMemcpyAsync(cm->h_keys.p, cm->d_keys.p, sizeof(unsigned long long) * HM_CM_CLASSES, hipMemcpyDeviceToHost, s));
     HM_HIP(hipStreamSynchronize(s));
     unsigned long long first[HM_CM_CLASSES];
-    memcpy(first, cm->h_keys, sizeof(first));
+    memcpy(first, cm->h_keys.p, sizeof(first));
     // the smallest j of each class's (d, i): a row pass of row i over partners (i, n), one per distinct i
     for (int q = 0; q < HM_CM_CLASSES; ++q) {
         uint32_t* o = out + 4 * q;
@@ -286,13 +277,13 @@ extern "C" int hm_classmin_build(hm_classmin* cm, float c, uint32_t* out, void* 
     for (int q = 0; q < HM_CM_CLASSES; ++q) {
         if (first[q] == ~0ull || out[4 * q] != 0) continue;
         const int64_t i = (int64_t)(uint32_t)first[q];
-        HM_HIP(hipMemsetAsync(cm->d_keys, 0xff, sizeof(unsigned long long) * HM_CM_SLOTS, s));
+        HM_HIP(hipMemsetAsync(cm->d_keys.p, 0xff, sizeof(unsigned long long) * HM_CM_SLOTS, s));
         if (int rc = hm_cm_row_launch(cm, i, i + 1, n, 0, sqrt_c, s)) return rc;
-        HM_HIP(hipMemcpyAsync(cm->h_keys, cm->d_keys, sizeof(unsigned long long) * HM_CM_CLASSES, hipMemcpyDeviceToHost, s));
+        HM_HIP(hipMemcpyAsync(cm->h_keys.p, cm->d_keys.p, sizeof(unsigned long long) * HM_CM_CLASSES, hipMemcpyDeviceToHost, s));
         HM_HIP(hipStreamSynchronize(s));
         for (int r = q; r < HM_CM_CLASSES; ++r) {          // every class whose minimum sits on row i
             if (first[r] == ~0ull || (int64_t)(uint32_t)first[r] != i) continue;
-            const unsigned long long k = cm->h_keys[r];
+            const unsigned long long k = cm->h_keys.p[r];
             if (k == ~0ull || (k >> 32) != (first[r] >> 32))
                 return hm_fail(e, HM_E_STATE, "hm_classmin_build: row pass disagrees with the pair pass (internal error)");
             uint32_t* o = out + 4 * r;
@@ -318,21 +309,16 @@ extern "C" int hm_classmin_fold(hm_classmin* cm, int64_t row, float c, const int
     HM_HIP(hipSetDevice(e->device));
     if (int rc = hm_cm_set_attrs(e)) return rc;
     hipStream_t s = (hipStream_t)stream;
-    if (n_partners > cm->partner_cap) {
-        if (cm->d_partners) (void)hipFree(cm->d_partners);
-        cm->d_partners = nullptr;
-        cm->partner_cap = 0;
-        const int64_t cap = std::max<int64_t>(1024, 2 * n_partners);
-        HM_HIP(hipMalloc(&cm->d_partners, sizeof(int32_t) * cap));
-        cm->partner_cap = cap;
+    if (n_partners > 0) {
+        HM_HIP(cm->d_partners.grow(std::max<int64_t>(1024, n_partners)));
+        HM_HIP(hipMemcpyAsync(cm->d_partners.p, partners, sizeof(int32_t) * n_partners, hipMemcpyHostToDevice, s));
     }
-    if (n_partners > 0) HM_HIP(hipMemcpyAsync(cm->d_partners, partners, sizeof(int32_t) * n_partners, hipMemcpyHostToDevice, s));
-    HM_HIP(hipMemsetAsync(cm->d_keys, 0xff, sizeof(unsigned long long) * HM_CM_SLOTS, s));
+    HM_HIP(hipMemsetAsync(cm->d_keys.p, 0xff, sizeof(unsigned long long) * HM_CM_SLOTS, s));
     if (int rc = hm_cm_row_launch(cm, row, 0, row, n_partners, sqrtf(c), s)) return rc;
-    HM_HIP(hipMemcpyAsync(cm->h_keys, cm->d_keys, sizeof(unsigned long long) * HM_CM_SLOTS, hipMemcpyDeviceToHost, s));
+    HM_HIP(hipMemcpyAsync(cm->h_keys.p, cm->d_keys.p, sizeof(unsigned long long) * HM_CM_SLOTS, hipMemcpyDeviceToHost, s));
     HM_HIP(hipStreamSynchronize(s));
     for (int q = 0; q < HM_CM_SLOTS; ++q) {
-        const unsigned long long k = cm->h_keys[q];
+        const unsigned long long k = cm->h_keys.p[q];
         uint32_t* o = out + 4 * q;
         if (k == ~0ull) { o[0] = 0; o[1] = 0; o[2] = 0xffffffffu; o[3] = 0xffffffffu; continue; }
         o[0] = 1; o[1] = (uint32_t)(k >> 32); o[2] = (uint32_t)k; o[3] = (uint32_t)row;

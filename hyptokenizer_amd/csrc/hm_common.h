@@ -5,6 +5,15 @@
 //   hm_search.hip   exact re-evaluation / selection kernels and the search entry points of the ABI
 //   hm_rows.hip     image construction, merge / midpoint, one-row-vs-all, gathered and row-wise kernels
 //   hm_loops.hip    device-resident merge loops (several steps per host call)
+//   hm_exact.hip    the prefilter-free search, last resort of the top-k search
+//   hm_comm.hip     the row-sharded search with its exchange step inside the library (RCCL)
+//   hm_rowgrad.hip, hm_contrastive.hip   backward kernels of the row-wise primitives; fused InfoNCE / triplet loss
+//   hm_retrieval.hip   recall@K ranks and exact k nearest keys
+//   hm_tokenize.hip    batch form of HyperbolicTokenizer.tokenize (engine-free, like the four below)
+//   hm_greedy.hip, hm_pairfreq.hip, hm_ngram.hip   the text side: greedy longest-match counts, adjacent-pair and n-gram
+//                   histograms of a corpus; hm_classmin.hip: per-class minima of the pair distance.  These four share
+//                   hm_table.h (owning device buffer, counting table, recount loop)
+//   hm_hostrng.cpp  host-only: prefix of torch.randperm
 //
 // Data layout in HBM: the fp32 "scan image" img[rows_alloc][RS], RS = 4*NG + 4 (+ 4 when needed to
 // make the 16-byte chunks per row odd), NG = groups of 4 spatial coordinates.  Group g holds spatial
@@ -57,8 +66,8 @@ typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 #define HM_PIPE_TAIL_MAX 8192u     // survivors a pipelined step's small tail grid takes (more: found = 2, that step goes through the host path)
 #define HM_ROWPASS_BLOCKS 256      // blocks of the one-row-vs-all reduction
 #define HM_PART_SLOTS 256          // partial records (>= HM_TAIL_BLOCKS, HM_ROWPASS_BLOCKS)
-#define HM_LOOP_MAX_STEPS 256
-#define HM_BATCH_MAX 4096          // merges per hm_merge_append_batch_host call       // steps one device-resident loop call may enqueue
+#define HM_LOOP_MAX_STEPS 256      // steps one device-resident loop call may enqueue
+#define HM_BATCH_MAX 4096          // merges per hm_merge_append_batch_host call
 
 // prefilter forms (hm_engine_create / hm_set_prefilter)
 #define HM_PREFILTER_AUTO 0

@@ -20,7 +20,7 @@
 //   phase 2  one wave per (line, 64 candidates), lines longest first: marked lanes walk the line, the others take
 //            base[l]; lanes of a wave share the line's cache lines.  counts[c][l] (optional) and
 //            totals[c] = sum_l mult[l] * count[c][l] (int64 atomics).
-#include "hm_common.h"
+#include "hm_table.h"
 
 namespace {
 
@@ -178,13 +178,8 @@ __global__ __launch_bounds__(64) void hm_greedy_walk_kernel(CountArgs a)
 struct hm_greedy {
     int device = 0;
     // corpus (device)
-    int32_t* cp = nullptr;
-    int32_t* line_of = nullptr;
-    int32_t* lm = nullptr;
-    int64_t* off = nullptr;
-    int64_t* mult = nullptr;
-    int32_t* base = nullptr;
-    int32_t* order = nullptr;
+    DevBuf<int32_t> cp, line_of, lm, base, order;
+    DevBuf<int64_t> off, mult;
     int64_t n = 0, n_lines = 0;
     bool has_corpus = false;
     // vocabulary (host pool; empty strings are kept out: they never match)
@@ -192,38 +187,12 @@ struct hm_greedy {
     std::vector<int64_t> pool_off{0};
     int32_t max_len = 0;
     // per-call workspaces (grown on demand)
-    int32_t* cand = nullptr;
-    int64_t cand_cap = 0;
-    int64_t* cand_off = nullptr;
-    int64_t cand_off_cap = 0;
-    uint8_t* mark = nullptr;
-    int64_t mark_cap = 0;
+    DevBuf<int32_t> cand;
+    DevBuf<int64_t> cand_off;
+    DevBuf<uint8_t> mark;
 };
 
 namespace {
-
-void hm_gr_free_corpus(hm_greedy* g)
-{
-    for (void* p : {(void*)g->cp, (void*)g->line_of, (void*)g->lm, (void*)g->off, (void*)g->mult, (void*)g->base, (void*)g->order})
-        if (p) (void)hipFree(p);
-    g->cp = g->line_of = g->lm = g->base = g->order = nullptr;
-    g->off = g->mult = nullptr;
-    g->n = g->n_lines = 0;
-    g->has_corpus = false;
-}
-
-template <class T>
-int hm_gr_grow(T** buf, int64_t* cap, int64_t need)
-{
-    if (need <= *cap) return HM_OK;
-    int64_t c = std::max<int64_t>(need, 2 * *cap);
-    if (*buf) (void)hipFree(*buf);
-    *buf = nullptr;
-    *cap = 0;
-    HM_HIP0(hipMalloc(buf, sizeof(T) * (size_t)std::max<int64_t>(c, 1)));
-    *cap = c;
-    return HM_OK;
-}
 
 // strings [s0, s1) of an offsets array: argument checks shared by the entry points
 int hm_gr_check_strings(const char* who, const int32_t* cps, const int64_t* offsets, int64_t count)
@@ -247,7 +216,7 @@ int hm_gr_rebuild(hm_greedy* g, hipStream_t st)
         // empty lines only: nothing to match, every count is 0
     } else if (n_str == 0) {
         std::vector<int32_t> ones((size_t)g->n, 1);
-        HM_HIP0(hipMemcpyAsync(g->lm, ones.data(), sizeof(int32_t) * g->n, hipMemcpyHostToDevice, st));
+        HM_HIP0(hipMemcpyAsync(g->lm.p, ones.data(), sizeof(int32_t) * g->n, hipMemcpyHostToDevice, st));
         HM_HIP0(hipStreamSynchronize(st));
     } else {
         int64_t cap = 16;
@@ -267,34 +236,25 @@ int hm_gr_rebuild(hm_greedy* g, hipStream_t st)
                 if (e.len == len && e.h == h && std::equal(t, t + len, g->pool.data() + g->pool_off[e.str])) break;   // duplicate
             }
         }
-        SetEntry* d_set = nullptr;
-        uint8_t* d_has = nullptr;
-        int32_t* d_pool = nullptr;
-        int64_t* d_poff = nullptr;
-        auto release = [&]() {
-            for (void* p : {(void*)d_set, (void*)d_has, (void*)d_pool, (void*)d_poff}) if (p) (void)hipFree(p);
-        };
-        hipError_t err = hipMalloc(&d_set, sizeof(SetEntry) * cap);
-        if (err == hipSuccess) err = hipMalloc(&d_has, has_len.size());
-        if (err == hipSuccess) err = hipMalloc(&d_pool, sizeof(int32_t) * std::max<size_t>(g->pool.size(), 1));
-        if (err == hipSuccess) err = hipMalloc(&d_poff, sizeof(int64_t) * g->pool_off.size());
-        if (err == hipSuccess) err = hipMemcpyAsync(d_set, set.data(), sizeof(SetEntry) * cap, hipMemcpyHostToDevice, st);
-        if (err == hipSuccess) err = hipMemcpyAsync(d_has, has_len.data(), has_len.size(), hipMemcpyHostToDevice, st);
-        if (err == hipSuccess && !g->pool.empty())
-            err = hipMemcpyAsync(d_pool, g->pool.data(), sizeof(int32_t) * g->pool.size(), hipMemcpyHostToDevice, st);
-        if (err == hipSuccess)
-            err = hipMemcpyAsync(d_poff, g->pool_off.data(), sizeof(int64_t) * g->pool_off.size(), hipMemcpyHostToDevice, st);
-        if (err == hipSuccess) {
-            hipLaunchKernelGGL(hm_greedy_build_kernel, dim3((unsigned)((g->n + 255) / 256)), dim3(256), 0, st,
-                               g->cp, g->line_of, g->off, g->n, d_set, mask, d_has, g->max_len, d_pool, d_poff, g->lm);
-            err = hipGetLastError();
-        }
-        if (err == hipSuccess) err = hipStreamSynchronize(st);     // the temporaries die here
-        release();
-        if (err != hipSuccess) return hm_fail(nullptr, (int)err, std::string("hm_greedy: lm build failed: ") + hipGetErrorString(err));
+        DevBuf<SetEntry> d_set;
+        DevBuf<uint8_t> d_has;
+        DevBuf<int32_t> d_pool;
+        DevBuf<int64_t> d_poff;
+        HM_HIP0(d_set.alloc(cap));
+        HM_HIP0(d_has.alloc((int64_t)has_len.size()));
+        HM_HIP0(d_pool.alloc((int64_t)g->pool.size()));
+        HM_HIP0(d_poff.alloc((int64_t)g->pool_off.size()));
+        HM_HIP0(hipMemcpyAsync(d_set.p, set.data(), sizeof(SetEntry) * cap, hipMemcpyHostToDevice, st));
+        HM_HIP0(hipMemcpyAsync(d_has.p, has_len.data(), has_len.size(), hipMemcpyHostToDevice, st));
+        if (!g->pool.empty()) HM_HIP0(hipMemcpyAsync(d_pool.p, g->pool.data(), sizeof(int32_t) * g->pool.size(), hipMemcpyHostToDevice, st));
+        HM_HIP0(hipMemcpyAsync(d_poff.p, g->pool_off.data(), sizeof(int64_t) * g->pool_off.size(), hipMemcpyHostToDevice, st));
+        hipLaunchKernelGGL(hm_greedy_build_kernel, dim3((unsigned)((g->n + 255) / 256)), dim3(256), 0, st,
+                           g->cp.p, g->line_of.p, g->off.p, g->n, d_set.p, mask, d_has.p, g->max_len, d_pool.p, d_poff.p, g->lm.p);
+        HM_HIP0(hipGetLastError());
+        HM_HIP0(hipStreamSynchronize(st));     // the temporaries die here
     }
     if (g->n_lines) {
-        hipLaunchKernelGGL(hm_greedy_base_kernel, dim3((unsigned)((g->n_lines + 63) / 64)), dim3(64), 0, st, g->off, g->lm, g->n_lines, g->base);
+        hipLaunchKernelGGL(hm_greedy_base_kernel, dim3((unsigned)((g->n_lines + 63) / 64)), dim3(64), 0, st, g->off.p, g->lm.p, g->n_lines, g->base.p);
         HM_HIP0(hipGetLastError());
     }
     HM_HIP0(hipStreamSynchronize(st));
@@ -305,12 +265,7 @@ int hm_gr_rebuild(hm_greedy* g, hipStream_t st)
 
 extern "C" int hm_greedy_create(hm_greedy** out, int device)
 {
-    if (!out) return hm_fail(nullptr, HM_E_ARG, "hm_greedy_create: out is NULL");
-    *out = nullptr;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-        return hm_fail(nullptr, HM_E_ARG, "hm_greedy_create: no HIP device available (the matcher has no CPU fallback)");
-    if (device < 0 || device >= ndev) return hm_fail(nullptr, HM_E_ARG, "hm_greedy_create: bad device index");
+    if (int e = hm_check_create("hm_greedy_create", out, device)) return e;
     hm_greedy* g = new hm_greedy();
     g->device = device;
     *out = g;
@@ -321,8 +276,6 @@ extern "C" int hm_greedy_destroy(hm_greedy* g)
 {
     if (!g) return HM_OK;
     (void)hipSetDevice(g->device);           // every entry point synchronises its stream: nothing is in flight
-    hm_gr_free_corpus(g);
-    for (void* p : {(void*)g->cand, (void*)g->cand_off, (void*)g->mark}) if (p) (void)hipFree(p);
     delete g;
     return HM_OK;
 }
@@ -339,7 +292,7 @@ extern "C" int hm_greedy_set_corpus(hm_greedy* g, const int32_t* cps, const int6
     HM_HIP0(hipSetDevice(g->device));
     hipStream_t st = (hipStream_t)stream;
     HM_HIP0(hipStreamSynchronize(st));          // earlier counts may still read the old corpus
-    hm_gr_free_corpus(g);
+    g->has_corpus = false;
     const int64_t n = n_lines ? offsets[n_lines] : 0;
     std::vector<int32_t> line_of((size_t)n);
     std::vector<int32_t> order((size_t)n_lines);
@@ -350,24 +303,23 @@ extern "C" int hm_greedy_set_corpus(hm_greedy* g, const int32_t* cps, const int6
     std::stable_sort(order.begin(), order.end(), [&](int32_t x, int32_t y) {
         return offsets[x + 1] - offsets[x] > offsets[y + 1] - offsets[y];
     });
-    const size_t nb = (size_t)std::max<int64_t>(n, 1), lb = (size_t)std::max<int64_t>(n_lines, 1);
-    HM_HIP0(hipMalloc(&g->cp, sizeof(int32_t) * nb));
-    HM_HIP0(hipMalloc(&g->line_of, sizeof(int32_t) * nb));
-    HM_HIP0(hipMalloc(&g->lm, sizeof(int32_t) * nb));
-    HM_HIP0(hipMalloc(&g->off, sizeof(int64_t) * (lb + 1)));
-    HM_HIP0(hipMalloc(&g->mult, sizeof(int64_t) * lb));
-    HM_HIP0(hipMalloc(&g->base, sizeof(int32_t) * lb));
-    HM_HIP0(hipMalloc(&g->order, sizeof(int32_t) * lb));
+    HM_HIP0(g->cp.alloc(n));
+    HM_HIP0(g->line_of.alloc(n));
+    HM_HIP0(g->lm.alloc(n));
+    HM_HIP0(g->off.alloc(n_lines + 1));
+    HM_HIP0(g->mult.alloc(n_lines));
+    HM_HIP0(g->base.alloc(n_lines));
+    HM_HIP0(g->order.alloc(n_lines));
     g->n = n;
     g->n_lines = n_lines;
     if (n) {
-        HM_HIP0(hipMemcpyAsync(g->cp, cps, sizeof(int32_t) * n, hipMemcpyHostToDevice, st));
-        HM_HIP0(hipMemcpyAsync(g->line_of, line_of.data(), sizeof(int32_t) * n, hipMemcpyHostToDevice, st));
+        HM_HIP0(hipMemcpyAsync(g->cp.p, cps, sizeof(int32_t) * n, hipMemcpyHostToDevice, st));
+        HM_HIP0(hipMemcpyAsync(g->line_of.p, line_of.data(), sizeof(int32_t) * n, hipMemcpyHostToDevice, st));
     }
     if (n_lines) {
-        HM_HIP0(hipMemcpyAsync(g->off, offsets, sizeof(int64_t) * (n_lines + 1), hipMemcpyHostToDevice, st));
-        HM_HIP0(hipMemcpyAsync(g->mult, mult, sizeof(int64_t) * n_lines, hipMemcpyHostToDevice, st));
-        HM_HIP0(hipMemcpyAsync(g->order, order.data(), sizeof(int32_t) * n_lines, hipMemcpyHostToDevice, st));
+        HM_HIP0(hipMemcpyAsync(g->off.p, offsets, sizeof(int64_t) * (n_lines + 1), hipMemcpyHostToDevice, st));
+        HM_HIP0(hipMemcpyAsync(g->mult.p, mult, sizeof(int64_t) * n_lines, hipMemcpyHostToDevice, st));
+        HM_HIP0(hipMemcpyAsync(g->order.p, order.data(), sizeof(int32_t) * n_lines, hipMemcpyHostToDevice, st));
     }
     HM_HIP0(hipStreamSynchronize(st));          // the host staging vectors die here
     g->has_corpus = true;
@@ -397,14 +349,14 @@ extern "C" int hm_greedy_add_strings(hm_greedy* g, const int32_t* cps, const int
     HM_HIP0(hipSetDevice(g->device));
     hipStream_t st = (hipStream_t)stream;
     if (n_new > HM_GR_DIRECT_MAX) return hm_gr_rebuild(g, st);
-    if (int e = hm_gr_grow(&g->cand, &g->cand_cap, fresh.back())) return e;
-    if (int e = hm_gr_grow(&g->cand_off, &g->cand_off_cap, n_new + 1)) return e;
-    HM_HIP0(hipMemcpyAsync(g->cand, g->pool.data() + pool0, sizeof(int32_t) * fresh.back(), hipMemcpyHostToDevice, st));
-    HM_HIP0(hipMemcpyAsync(g->cand_off, fresh.data(), sizeof(int64_t) * fresh.size(), hipMemcpyHostToDevice, st));
+    HM_HIP0(g->cand.grow(fresh.back()));
+    HM_HIP0(g->cand_off.grow(n_new + 1));
+    HM_HIP0(hipMemcpyAsync(g->cand.p, g->pool.data() + pool0, sizeof(int32_t) * fresh.back(), hipMemcpyHostToDevice, st));
+    HM_HIP0(hipMemcpyAsync(g->cand_off.p, fresh.data(), sizeof(int64_t) * fresh.size(), hipMemcpyHostToDevice, st));
     hipLaunchKernelGGL(hm_greedy_append_kernel, dim3((unsigned)((g->n + 255) / 256)), dim3(256), 0, st,
-                       g->cp, g->line_of, g->off, g->n, g->cand, g->cand_off, (int32_t)n_new, g->lm);
+                       g->cp.p, g->line_of.p, g->off.p, g->n, g->cand.p, g->cand_off.p, (int32_t)n_new, g->lm.p);
     HM_HIP0(hipGetLastError());
-    hipLaunchKernelGGL(hm_greedy_base_kernel, dim3((unsigned)((g->n_lines + 63) / 64)), dim3(64), 0, st, g->off, g->lm, g->n_lines, g->base);
+    hipLaunchKernelGGL(hm_greedy_base_kernel, dim3((unsigned)((g->n_lines + 63) / 64)), dim3(64), 0, st, g->off.p, g->lm.p, g->n_lines, g->base.p);
     HM_HIP0(hipGetLastError());
     HM_HIP0(hipStreamSynchronize(st));          // `fresh` and the pool may move once this returns
     return HM_OK;
@@ -423,17 +375,17 @@ extern "C" int hm_greedy_count(hm_greedy* g, const int32_t* cps, const int64_t* 
     hipStream_t st = (hipStream_t)stream;
     HM_HIP0(hipMemsetAsync(totals_dev, 0, sizeof(int64_t) * k, st));
     if (g->n_lines == 0) return HM_OK;
-    if (int e = hm_gr_grow(&g->cand, &g->cand_cap, offsets[k])) return e;
-    if (int e = hm_gr_grow(&g->cand_off, &g->cand_off_cap, k + 1)) return e;
-    if (int e = hm_gr_grow(&g->mark, &g->mark_cap, k * g->n_lines)) return e;
-    if (offsets[k]) HM_HIP0(hipMemcpyAsync(g->cand, cps, sizeof(int32_t) * offsets[k], hipMemcpyHostToDevice, st));
-    HM_HIP0(hipMemcpyAsync(g->cand_off, offsets, sizeof(int64_t) * (k + 1), hipMemcpyHostToDevice, st));
-    HM_HIP0(hipMemsetAsync(g->mark, 0, (size_t)(k * g->n_lines), st));
+    HM_HIP0(g->cand.grow(offsets[k]));
+    HM_HIP0(g->cand_off.grow(k + 1));
+    HM_HIP0(g->mark.grow(k * g->n_lines));
+    if (offsets[k]) HM_HIP0(hipMemcpyAsync(g->cand.p, cps, sizeof(int32_t) * offsets[k], hipMemcpyHostToDevice, st));
+    HM_HIP0(hipMemcpyAsync(g->cand_off.p, offsets, sizeof(int64_t) * (k + 1), hipMemcpyHostToDevice, st));
+    HM_HIP0(hipMemsetAsync(g->mark.p, 0, (size_t)(k * g->n_lines), st));
     CountArgs a;
-    a.cp = g->cp; a.line_of = g->line_of; a.off = g->off; a.mult = g->mult; a.lm = g->lm; a.base = g->base; a.order = g->order;
+    a.cp = g->cp.p; a.line_of = g->line_of.p; a.off = g->off.p; a.mult = g->mult.p; a.lm = g->lm.p; a.base = g->base.p; a.order = g->order.p;
     a.n = g->n; a.n_lines = g->n_lines;
-    a.cand = g->cand; a.cand_off = g->cand_off; a.k = (int32_t)k; a.k_waves = (int32_t)((k + 63) / 64);
-    a.mark = g->mark; a.counts = counts_dev; a.totals = reinterpret_cast<unsigned long long*>(totals_dev);
+    a.cand = g->cand.p; a.cand_off = g->cand_off.p; a.k = (int32_t)k; a.k_waves = (int32_t)((k + 63) / 64);
+    a.mark = g->mark.p; a.counts = counts_dev; a.totals = reinterpret_cast<unsigned long long*>(totals_dev);
     if (g->n) {
         hipLaunchKernelGGL(hm_greedy_mark_kernel, dim3((unsigned)((g->n + 255) / 256)), dim3(256), 0, st, a);
         HM_HIP0(hipGetLastError());
@@ -452,7 +404,7 @@ extern "C" int hm_greedy_longest(hm_greedy* g, int32_t* lm_dev, int32_t* base_de
     if (!g->has_corpus) return hm_fail(nullptr, HM_E_STATE, "hm_greedy_longest: hm_greedy_set_corpus first");
     HM_HIP0(hipSetDevice(g->device));
     hipStream_t st = (hipStream_t)stream;
-    if (lm_dev && g->n) HM_HIP0(hipMemcpyAsync(lm_dev, g->lm, sizeof(int32_t) * g->n, hipMemcpyDeviceToDevice, st));
-    if (base_dev && g->n_lines) HM_HIP0(hipMemcpyAsync(base_dev, g->base, sizeof(int32_t) * g->n_lines, hipMemcpyDeviceToDevice, st));
+    if (lm_dev && g->n) HM_HIP0(hipMemcpyAsync(lm_dev, g->lm.p, sizeof(int32_t) * g->n, hipMemcpyDeviceToDevice, st));
+    if (base_dev && g->n_lines) HM_HIP0(hipMemcpyAsync(base_dev, g->base.p, sizeof(int32_t) * g->n_lines, hipMemcpyDeviceToDevice, st));
     return HM_OK;
 }

@@ -16,81 +16,39 @@
 // key, 64-bit add, 64-bit min).  A key that finds no LDS slot within HM_PF_LDS_PROBES goes to the global table at once.
 // Skewed text (a few pairs dominate) thus costs one global atomic per block and key instead of one per occurrence.
 //
-// Capacity: every slab is counted into a slab table of its own whose load is capped at one half; crossing the cap (or
-// a probe sequence longer than HM_PF_SLAB_PROBES) raises an overflow flag, after which the table takes no new key and
-// the remaining blocks return at once; the host recounts the slab into a table four times larger (a table of
-// 2 * positions slots cannot overflow).  The first slab's table becomes the counter's main table; a later slab's table
-// is merged into it, after the main table has been grown (rehash on the device) to hold the exact number of distinct
-// keys both hold, so the main table never overflows.
-#include "hm_common.h"
-
-#include <algorithm>
-#include <vector>
+// Capacity: every slab is counted into a slab table (hm_table.h) of its own; when that overflows, the remaining blocks return
+// at once and the host recounts the slab into a table four times larger (hm_count_growing; a table of 2 * positions slots
+// cannot overflow).  The first slab's table becomes the counter's main table; a later slab's table is merged into it, after
+// the main table has been grown (rehash on the device) to hold the exact number of distinct keys both hold, so the main table
+// never overflows.
+#include "hm_table.h"
 
 struct hm_pairfreq;
 
 namespace {
 
-constexpr unsigned long long HM_PF_EMPTY = ~0ull;
 constexpr int64_t HM_PF_BIAS = 0x10FFFF + 2;                // -(2 + 0x10FFFF) -> 0
 constexpr int HM_PF_BITS = 22;                              // 2^21 + HM_PF_BIAS < 2^22
-constexpr unsigned long long HM_PF_FIELD = (1ull << HM_PF_BITS) - 1;   // a key never reaches HM_PF_EMPTY
+constexpr unsigned long long HM_PF_FIELD = (1ull << HM_PF_BITS) - 1;   // a key never reaches HM_TABLE_EMPTY
 constexpr int HM_PF_THREADS = 256;
 constexpr int HM_PF_ITEMS = 32;                             // positions per thread: 8192 per block
 constexpr int HM_PF_LDS_SLOTS = 4096;                       // 16 bytes each: 64 KiB
 constexpr int HM_PF_LDS_PROBES = 32;
-constexpr uint64_t HM_PF_SLAB_PROBES = 4096;                // a slab table that needs more is recounted larger
-
-__host__ __device__ __forceinline__ uint64_t hm_pf_mix(uint64_t k)
-{
-    k ^= k >> 31;
-    k *= 0x7fb5d329728ea185ull;
-    k ^= k >> 27;
-    k *= 0x81dadef4bc2dd44dull;
-    k ^= k >> 33;
-    return k;
-}
 
 struct PfTable {
-    unsigned long long* keys;     // [cap], HM_PF_EMPTY when free
+    HmTable t;                    // a slab table gives up after HM_TABLE_PROBES probes; the main table, sized to its exact
+                                  // key count, probes up to the whole table
     unsigned long long* counts;   // [cap]
     unsigned long long* first;    // [cap] smallest flat position
-    unsigned long long* distinct; // occupied slots
-    int* overflow;                // set when more than `limit` slots were taken (or a probe ran round the table)
-    uint64_t mask;                // cap - 1
-    unsigned long long limit;     // cap / 2: load at most one half
-    uint64_t max_probe;
 };
 
-__device__ __forceinline__ bool hm_pf_overflowed(const PfTable& t)
-{
-    return __hip_atomic_load(t.overflow, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0;
-}
-
-// A slab table stops taking keys once it has overflowed (the slab is recounted), and gives up after max_probe probes;
-// the main table is sized to its exact key count and probes up to the whole table.
 __device__ __forceinline__ void hm_pf_insert(const PfTable& t, unsigned long long key, unsigned long long cnt,
                                              unsigned long long pos)
 {
-    uint64_t h = hm_pf_mix(key) & t.mask;
-    for (uint64_t probe = 0; probe < t.max_probe; ++probe) {
-        unsigned long long cur = __hip_atomic_load(&t.keys[h], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (cur == HM_PF_EMPTY) {
-            if (hm_pf_overflowed(t)) return;
-            cur = atomicCAS(&t.keys[h], HM_PF_EMPTY, key);
-            if (cur == HM_PF_EMPTY) {
-                if (atomicAdd(t.distinct, 1ull) >= t.limit) atomicOr(t.overflow, 1);
-                cur = key;
-            }
-        }
-        if (cur == key) {
-            atomicAdd(&t.counts[h], cnt);
-            atomicMin(&t.first[h], pos);
-            return;
-        }
-        h = (h + 1) & t.mask;
-    }
-    atomicOr(t.overflow, 1);
+    const int64_t s = hm_table_claim(t.t, hm_mix64(key), key, [key](unsigned long long cur) { return cur == key; });
+    if (s < 0) return;
+    atomicAdd(&t.counts[s], cnt);
+    atomicMin(&t.first[s], pos);
 }
 
 __device__ __forceinline__ int64_t hm_pf_len(const int64_t* __restrict__ off, const int32_t* __restrict__ len, int64_t l)
@@ -135,13 +93,13 @@ __global__ __launch_bounds__(HM_PF_THREADS) void hm_pf_count_kernel(CountArgs a)
     __shared__ uint32_t s_min[HM_PF_LDS_SLOTS];
     __shared__ uint32_t s_pairs;
     for (int s = threadIdx.x; s < HM_PF_LDS_SLOTS; s += HM_PF_THREADS) {
-        s_key[s] = HM_PF_EMPTY;
+        s_key[s] = HM_TABLE_EMPTY;
         s_cnt[s] = 0;
         s_min[s] = 0xFFFFFFFFu;
     }
     if (threadIdx.x == 0) s_pairs = 0;
     __syncthreads();
-    if (hm_pf_overflowed(a.t)) return;                      // this slab is counted again into a larger table
+    if (hm_table_overflowed(a.t.t)) return;                      // this slab is counted again into a larger table
 
     const int64_t q0 = (int64_t)blockIdx.x * (HM_PF_THREADS * HM_PF_ITEMS);
     int64_t line = -1, line_next = 0, line_end = 0;         // [off[line], line_end): positions whose successor is in the line
@@ -169,11 +127,11 @@ __global__ __launch_bounds__(HM_PF_THREADS) void hm_pf_count_kernel(CountArgs a)
                                      | (((unsigned long long)((int64_t)a.sym[q + 1] + HM_PF_BIAS)) & HM_PF_FIELD);
         const uint32_t rel = (uint32_t)(q - q0);
         ++mine;
-        uint32_t h = (uint32_t)hm_pf_mix(key) & (HM_PF_LDS_SLOTS - 1);
+        uint32_t h = (uint32_t)hm_mix64(key) & (HM_PF_LDS_SLOTS - 1);
         bool done = false;
         for (int probe = 0; probe < HM_PF_LDS_PROBES; ++probe) {
-            const unsigned long long cur = atomicCAS(&s_key[h], HM_PF_EMPTY, key);
-            if (cur == HM_PF_EMPTY || cur == key) {
+            const unsigned long long cur = atomicCAS(&s_key[h], HM_TABLE_EMPTY, key);
+            if (cur == HM_TABLE_EMPTY || cur == key) {
                 atomicAdd(&s_cnt[h], 1u);
                 atomicMin(&s_min[h], rel);
                 done = true;
@@ -187,7 +145,7 @@ __global__ __launch_bounds__(HM_PF_THREADS) void hm_pf_count_kernel(CountArgs a)
     __syncthreads();
     for (int s = threadIdx.x; s < HM_PF_LDS_SLOTS; s += HM_PF_THREADS) {
         const unsigned long long key = s_key[s];
-        if (key != HM_PF_EMPTY)
+        if (key != HM_TABLE_EMPTY)
             hm_pf_insert(a.t, key, (unsigned long long)s_cnt[s], a.base + (unsigned long long)(q0 + s_min[s]));
     }
     if (threadIdx.x == 0 && s_pairs) atomicAdd(a.pairs, (unsigned long long)s_pairs);
@@ -201,31 +159,12 @@ __global__ __launch_bounds__(256) void hm_pf_merge_kernel(const unsigned long lo
     const uint64_t s = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (s >= cap) return;
     const unsigned long long key = keys[s];
-    if (key != HM_PF_EMPTY) hm_pf_insert(dst, key, counts[s], first[s]);
-}
-
-// occupied slots, compacted in any order (the host sorts by first position, which is unique per key)
-__global__ __launch_bounds__(256) void hm_pf_compact_kernel(PfTable t, uint64_t cap, unsigned long long* __restrict__ n_out,
-                                                            unsigned long long* __restrict__ keys_out,
-                                                            unsigned long long* __restrict__ counts_out,
-                                                            unsigned long long* __restrict__ first_out, uint64_t out_cap)
-{
-    const uint64_t s = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (s >= cap) return;
-    const unsigned long long key = t.keys[s];
-    if (key == HM_PF_EMPTY) return;
-    const unsigned long long k = atomicAdd(n_out, 1ull);
-    if (k >= out_cap) return;
-    keys_out[k] = key;
-    counts_out[k] = t.counts[s];
-    first_out[k] = t.first[s];
+    if (key != HM_TABLE_EMPTY) hm_pf_insert(dst, key, counts[s], first[s]);
 }
 
 struct Table {
-    unsigned long long* keys = nullptr;
-    unsigned long long* counts = nullptr;
-    unsigned long long* first = nullptr;
-    int64_t cap = 0;
+    DevBuf<unsigned long long> keys, counts, first;
+    int64_t cap() const { return keys.cap; }
 };
 
 // [0] main distinct  [1] slab distinct  [2] slab pairs  [3] compact count  [4] flags (two ints: slab, main overflow)
@@ -238,72 +177,54 @@ struct hm_pairfreq {
     int64_t init_cap = 0;
     bool forced = false;                                    // initial capacity given by the caller (test hook)
     Table main, slab;
-    unsigned long long* words = nullptr;
+    DevBuf<unsigned long long> words;
     int64_t n_distinct = 0;                                 // occupied slots of the main table
     int64_t n_pairs = 0;
     int64_t slab_recounts = 0;
+    int* flags() const { return reinterpret_cast<int*>(words.p + 4); }
 };
 
 namespace {
 
-void hm_pf_free(Table& t)
+// an empty table of `cap` slots
+int hm_pf_reset(Table& t, int64_t cap, hipStream_t st)
 {
-    for (void* p : {(void*)t.keys, (void*)t.counts, (void*)t.first}) if (p) (void)hipFree(p);
-    t = Table{};
-}
-
-int hm_pf_alloc(Table& t, int64_t cap, hipStream_t st)
-{
-    hm_pf_free(t);
-    HM_HIP0(hipMalloc(&t.keys, sizeof(unsigned long long) * cap));
-    HM_HIP0(hipMalloc(&t.counts, sizeof(unsigned long long) * cap));
-    HM_HIP0(hipMalloc(&t.first, sizeof(unsigned long long) * cap));
-    t.cap = cap;
-    HM_HIP0(hipMemsetAsync(t.keys, 0xFF, sizeof(unsigned long long) * cap, st));
-    HM_HIP0(hipMemsetAsync(t.counts, 0, sizeof(unsigned long long) * cap, st));
-    HM_HIP0(hipMemsetAsync(t.first, 0xFF, sizeof(unsigned long long) * cap, st));
-    return HM_OK;
+    if (int e = hm_column_reset(t.keys, cap, 0xFF, st)) return e;
+    if (int e = hm_column_reset(t.counts, cap, 0, st)) return e;
+    return hm_column_reset(t.first, cap, 0xFF, st);
 }
 
 PfTable hm_pf_view(const Table& t, unsigned long long* distinct, int* overflow, bool slab = false)
 {
-    PfTable v;
-    v.keys = t.keys; v.counts = t.counts; v.first = t.first;
-    v.distinct = distinct; v.overflow = overflow;
-    v.mask = (uint64_t)t.cap - 1;
-    v.limit = (unsigned long long)(t.cap / 2);
-    v.max_probe = slab ? std::min<uint64_t>(HM_PF_SLAB_PROBES, (uint64_t)t.cap) : (uint64_t)t.cap;
-    return v;
+    return PfTable{hm_table_view(t.keys.p, t.cap(), distinct, overflow, slab), t.counts.p, t.first.p};
 }
 
-int64_t hm_pf_pow2(int64_t x)
+int64_t hm_pf_pow2(int64_t x) { return hm_pow2_at_least(x, 4); }
+
+// every occupied slot of `src` into `dst` (the main table, or its successor), whose distinct count and overflow flag come
+// back in `words`
+int hm_pf_merge(hm_pairfreq* pf, const Table& src, const Table& dst, unsigned long long* words, hipStream_t st)
 {
-    int64_t c = 4;
-    while (c < x) c <<= 1;
-    return c;
+    HM_HIP0(hipMemsetAsync(pf->flags() + 1, 0, sizeof(int), st));
+    hipLaunchKernelGGL(hm_pf_merge_kernel, dim3(hm_blocks(src.cap(), 256)), dim3(256), 0, st, src.keys.p, src.counts.p, src.first.p,
+                       (uint64_t)src.cap(), hm_pf_view(dst, pf->words.p, pf->flags() + 1));
+    HM_HIP0(hipGetLastError());
+    HM_HIP0(hipMemcpyAsync(words, pf->words.p, sizeof(unsigned long long) * HM_PF_WORDS, hipMemcpyDeviceToHost, st));
+    HM_HIP0(hipStreamSynchronize(st));
+    return HM_OK;
 }
-
-unsigned hm_pf_blocks(int64_t n, int per) { return (unsigned)((n + per - 1) / per); }
 
 // main table able to hold `need` distinct keys at load <= 1/2 (rehash of what it holds)
 int hm_pf_reserve_main(hm_pairfreq* pf, int64_t need, hipStream_t st)
 {
-    if (pf->main.cap && need <= pf->main.cap / 2) return HM_OK;
-    const int64_t cap = hm_pf_pow2(std::max<int64_t>(2 * need, pf->init_cap));
+    if (pf->main.cap() && need <= pf->main.cap() / 2) return HM_OK;
     Table fresh;
-    if (int e = hm_pf_alloc(fresh, cap, st)) { hm_pf_free(fresh); return e; }
-    int* flags = reinterpret_cast<int*>(pf->words + 4);
-    HM_HIP0(hipMemsetAsync(pf->words, 0, sizeof(unsigned long long), st));
-    HM_HIP0(hipMemsetAsync(flags + 1, 0, sizeof(int), st));
-    if (pf->main.cap) {
-        hipLaunchKernelGGL(hm_pf_merge_kernel, dim3(hm_pf_blocks(pf->main.cap, 256)), dim3(256), 0, st,
-                           pf->main.keys, pf->main.counts, pf->main.first, (uint64_t)pf->main.cap,
-                           hm_pf_view(fresh, pf->words, flags + 1));
-        HM_HIP0(hipGetLastError());
-    }
-    HM_HIP0(hipStreamSynchronize(st));
-    hm_pf_free(pf->main);
-    pf->main = fresh;
+    if (int e = hm_pf_reset(fresh, hm_pf_pow2(std::max<int64_t>(2 * need, pf->init_cap)), st)) return e;
+    HM_HIP0(hipMemsetAsync(pf->words.p, 0, sizeof(unsigned long long), st));
+    unsigned long long words[HM_PF_WORDS];
+    if (pf->main.cap())
+        if (int e = hm_pf_merge(pf, pf->main, fresh, words, st)) return e;
+    pf->main = std::move(fresh);
     return HM_OK;
 }
 
@@ -311,26 +232,15 @@ int hm_pf_reserve_main(hm_pairfreq* pf, int64_t need, hipStream_t st)
 
 extern "C" int hm_pairfreq_create(hm_pairfreq** out, int device, int64_t initial_capacity)
 {
-    if (!out) return hm_fail(nullptr, HM_E_ARG, "hm_pairfreq_create: out is NULL");
-    *out = nullptr;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-        return hm_fail(nullptr, HM_E_ARG, "hm_pairfreq_create: no HIP device available (the counter has no CPU fallback)");
-    if (device < 0 || device >= ndev) return hm_fail(nullptr, HM_E_ARG, "hm_pairfreq_create: bad device index");
-    if (initial_capacity < 0 || initial_capacity > ((int64_t)1 << 40))
-        return hm_fail(nullptr, HM_E_ARG, "hm_pairfreq_create: initial_capacity must lie in [0, 2^40]");
+    if (int e = hm_check_create("hm_pairfreq_create", out, device, initial_capacity)) return e;
     HM_HIP0(hipSetDevice(device));
-    hm_pairfreq* pf = new hm_pairfreq();
+    std::unique_ptr<hm_pairfreq> pf(new hm_pairfreq());
     pf->device = device;
     pf->init_cap = hm_pf_pow2(initial_capacity ? initial_capacity : ((int64_t)1 << 16));
     pf->forced = initial_capacity != 0;
-    if (hipMalloc(&pf->words, sizeof(unsigned long long) * HM_PF_WORDS) != hipSuccess
-        || hipMemset(pf->words, 0, sizeof(unsigned long long) * HM_PF_WORDS) != hipSuccess) {
-        if (pf->words) (void)hipFree(pf->words);
-        delete pf;
+    if (pf->words.alloc(HM_PF_WORDS) != hipSuccess || hipMemset(pf->words.p, 0, sizeof(unsigned long long) * HM_PF_WORDS) != hipSuccess)
         return hm_fail(nullptr, HM_E_NOMEM, "hm_pairfreq_create: device allocation failed");
-    }
-    *out = pf;
+    *out = pf.release();
     return HM_OK;
 }
 
@@ -338,9 +248,6 @@ extern "C" int hm_pairfreq_destroy(hm_pairfreq* pf)
 {
     if (!pf) return HM_OK;
     (void)hipSetDevice(pf->device);          // every entry point synchronises its stream: nothing is in flight
-    hm_pf_free(pf->main);
-    hm_pf_free(pf->slab);
-    if (pf->words) (void)hipFree(pf->words);
     delete pf;
     return HM_OK;
 }
@@ -356,41 +263,27 @@ extern "C" int hm_pairfreq_add(hm_pairfreq* pf, const int32_t* sym_dev, const in
     if (n_lines == 0 || n_positions < 2) return HM_OK;
     HM_HIP0(hipSetDevice(pf->device));
     hipStream_t st = (hipStream_t)stream;
-    unsigned long long* slab_distinct = pf->words + 1;
-    unsigned long long* slab_pairs = pf->words + 2;
-    int* flags = reinterpret_cast<int*>(pf->words + 4);
     const int64_t bound = hm_pf_pow2(2 * n_positions);     // load <= 1/2 with every position a distinct pair
     // first guess: what earlier slabs needed, and (unless a tiny capacity was forced) one slot per 8 positions, at most 2^25
-    int64_t guess = std::max<int64_t>(pf->init_cap, std::max<int64_t>(pf->slab.cap, 2 * pf->n_distinct));
+    int64_t guess = std::max<int64_t>(pf->init_cap, std::max<int64_t>(pf->slab.cap(), 2 * pf->n_distinct));
     if (!pf->forced) guess = std::max<int64_t>(guess, std::min<int64_t>(n_positions / 8, (int64_t)1 << 25));
-    int64_t cap = std::min(bound, hm_pf_pow2(guess));
     unsigned long long words[HM_PF_WORDS];
-    for (;;) {
-        if (pf->slab.cap != cap) {
-            if (int e = hm_pf_alloc(pf->slab, cap, st)) return e;
-        } else {
-            HM_HIP0(hipMemsetAsync(pf->slab.keys, 0xFF, sizeof(unsigned long long) * cap, st));
-            HM_HIP0(hipMemsetAsync(pf->slab.counts, 0, sizeof(unsigned long long) * cap, st));
-            HM_HIP0(hipMemsetAsync(pf->slab.first, 0xFF, sizeof(unsigned long long) * cap, st));
-        }
-        HM_HIP0(hipMemsetAsync(pf->words + 1, 0, sizeof(unsigned long long) * 2, st));
-        HM_HIP0(hipMemsetAsync(flags, 0, sizeof(int), st));
+    auto count = [&](int64_t cap, bool* overflow) -> int {
+        if (int e = hm_pf_reset(pf->slab, cap, st)) return e;
+        HM_HIP0(hipMemsetAsync(pf->words.p + 1, 0, sizeof(unsigned long long) * 2, st));
+        HM_HIP0(hipMemsetAsync(pf->flags(), 0, sizeof(int), st));
         CountArgs a;
         a.sym = sym_dev; a.off = offsets_dev; a.len = len_dev; a.n_lines = n_lines; a.n = n_positions;
-        a.base = (unsigned long long)base; a.pairs = slab_pairs;
-        a.t = hm_pf_view(pf->slab, slab_distinct, flags, cap < bound);   // at the bound: probe the whole table
-        hipLaunchKernelGGL(hm_pf_count_kernel, dim3(hm_pf_blocks(n_positions, HM_PF_THREADS * HM_PF_ITEMS)),
-                           dim3(HM_PF_THREADS), 0, st, a);
+        a.base = (unsigned long long)base; a.pairs = pf->words.p + 2;
+        a.t = hm_pf_view(pf->slab, pf->words.p + 1, pf->flags(), cap < bound);   // at the bound: probe the whole table
+        hipLaunchKernelGGL(hm_pf_count_kernel, dim3(hm_blocks(n_positions, HM_PF_THREADS * HM_PF_ITEMS)), dim3(HM_PF_THREADS), 0, st, a);
         HM_HIP0(hipGetLastError());
-        HM_HIP0(hipMemcpyAsync(words, pf->words, sizeof(words), hipMemcpyDeviceToHost, st));
+        HM_HIP0(hipMemcpyAsync(words, pf->words.p, sizeof(words), hipMemcpyDeviceToHost, st));
         HM_HIP0(hipStreamSynchronize(st));
-        const int* fl = reinterpret_cast<const int*>(words + 4);
-        if (!fl[0]) break;
-        if (cap >= bound)
-            return hm_fail(nullptr, HM_E_STATE, "hm_pairfreq_add: overflow of a table sized for every position (internal error)");
-        cap = std::min(bound, 4 * cap);                     // recount the slab into a larger table
-        ++pf->slab_recounts;
-    }
+        *overflow = reinterpret_cast<const int*>(words + 4)[0] != 0;
+        return HM_OK;
+    };
+    if (int e = hm_count_growing("hm_pairfreq_add", std::min(bound, hm_pf_pow2(guess)), bound, pf->slab_recounts, count)) return e;
     const int64_t slab_n = (int64_t)words[1];
     pf->n_pairs += (int64_t)words[2];
     if (pf->n_distinct == 0) {                              // nothing counted yet: the slab table becomes the main table
@@ -399,13 +292,8 @@ extern "C" int hm_pairfreq_add(hm_pairfreq* pf, const int32_t* sym_dev, const in
         return HM_OK;
     }
     if (int e = hm_pf_reserve_main(pf, pf->n_distinct + slab_n, st)) return e;
-    HM_HIP0(hipMemcpyAsync(pf->words, &pf->n_distinct, sizeof(int64_t), hipMemcpyHostToDevice, st));
-    HM_HIP0(hipMemsetAsync(flags + 1, 0, sizeof(int), st));
-    hipLaunchKernelGGL(hm_pf_merge_kernel, dim3(hm_pf_blocks(cap, 256)), dim3(256), 0, st,
-                       pf->slab.keys, pf->slab.counts, pf->slab.first, (uint64_t)cap, hm_pf_view(pf->main, pf->words, flags + 1));
-    HM_HIP0(hipGetLastError());
-    HM_HIP0(hipMemcpyAsync(words, pf->words, sizeof(words), hipMemcpyDeviceToHost, st));
-    HM_HIP0(hipStreamSynchronize(st));
+    HM_HIP0(hipMemcpyAsync(pf->words.p, &pf->n_distinct, sizeof(int64_t), hipMemcpyHostToDevice, st));
+    if (int e = hm_pf_merge(pf, pf->slab, pf->main, words, st)) return e;
     if (reinterpret_cast<const int*>(words + 4)[1])
         return hm_fail(nullptr, HM_E_STATE, "hm_pairfreq_add: main table overflow (internal error)");
     pf->n_distinct = (int64_t)words[0];
@@ -425,12 +313,11 @@ extern "C" int hm_pairfreq_read(hm_pairfreq* pf, int64_t* n_distinct, int64_t* n
     if (pf->n_distinct == 0) return HM_OK;
     HM_HIP0(hipSetDevice(pf->device));
     hipStream_t st = (hipStream_t)stream;
-    HM_HIP0(hipMemsetAsync(pf->words + 3, 0, sizeof(unsigned long long), st));
-    hipLaunchKernelGGL(hm_pf_compact_kernel, dim3(hm_pf_blocks(pf->main.cap, 256)), dim3(256), 0, st,
-                       hm_pf_view(pf->main, pf->words, reinterpret_cast<int*>(pf->words + 4) + 1), (uint64_t)pf->main.cap,
-                       pf->words + 3, reinterpret_cast<unsigned long long*>(keys_dev),
-                       reinterpret_cast<unsigned long long*>(counts_dev), reinterpret_cast<unsigned long long*>(first_dev),
-                       (uint64_t)out_cap);
+    HM_HIP0(hipMemsetAsync(pf->words.p + 3, 0, sizeof(unsigned long long), st));
+    HmColumns<2> cols{{pf->main.counts.p, pf->main.first.p},
+                      {reinterpret_cast<unsigned long long*>(counts_dev), reinterpret_cast<unsigned long long*>(first_dev)}};
+    hipLaunchKernelGGL(hm_table_compact_kernel<2>, dim3(hm_blocks(pf->main.cap(), 256)), dim3(256), 0, st, pf->main.keys.p, cols,
+                       (uint64_t)pf->main.cap(), pf->words.p + 3, reinterpret_cast<unsigned long long*>(keys_dev), (uint64_t)out_cap);
     HM_HIP0(hipGetLastError());
     HM_HIP0(hipStreamSynchronize(st));
     return HM_OK;

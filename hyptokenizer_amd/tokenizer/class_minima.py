@@ -17,7 +17,8 @@ import ctypes as C
 from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
-import torch
+
+from .._handle import DeviceHandle
 
 N_CODES, N_CLASSES = 10, 55
 Best = Optional[Tuple[float, int, int]]
@@ -65,51 +66,33 @@ def _records(out: np.ndarray, count: int) -> List[Best]:
     return [(float(f32[q]), int(r[q, 2]), int(r[q, 3])) if r[q, 0] else None for q in range(count)]
 
 
-class DeviceBackend:
+class DeviceBackend(DeviceHandle):
     """``hm_classmin`` on a ``MergeEngine``."""
 
+    PREFIX = "hm_classmin"
+
     def __init__(self, eng):
-        from .. import _lib
-        self._lib = _lib
-        self._L = _lib.load()
+        super().__init__(engine=eng)
         self.eng = eng
-        h = C.c_void_p(0)
-        _lib.check(self._L.hm_classmin_create(C.byref(h), eng._h), eng._h)
-        self._h = h
-        self._out = np.zeros(4 * _lib.CM_SLOTS, np.uint32)
+        self._out = np.zeros(4 * self._lib.CM_SLOTS, np.uint32)
         self.calls = {"build": 0, "fold": 0}
-
-    def close(self) -> None:
-        if getattr(self, "_h", None) is not None and self._h.value:
-            self._L.hm_classmin_destroy(self._h)
-            self._h = C.c_void_p(0)
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def _stream(self):
-        return C.c_void_p(torch.cuda.current_stream(self.eng.device).cuda_stream)
 
     def set_codes(self, codes: np.ndarray, row_begin: int) -> None:
         a = np.ascontiguousarray(codes, np.uint8)
-        self._lib.check(self._L.hm_classmin_set_codes(self._h, C.c_void_p(a.ctypes.data), int(row_begin),
-                                                      int(row_begin) + len(a), self._stream()), self.eng._h)
+        self._check(self._L.hm_classmin_set_codes(self._h, C.c_void_p(a.ctypes.data), int(row_begin),
+                                                  int(row_begin) + len(a), self._stream()))
 
     def build(self, c: float) -> List[Best]:
         self.calls["build"] += 1
-        self._lib.check(self._L.hm_classmin_build(self._h, float(c), C.c_void_p(self._out.ctypes.data), self._stream()),
-                        self.eng._h)
+        self._check(self._L.hm_classmin_build(self._h, float(c), C.c_void_p(self._out.ctypes.data), self._stream()))
         return _records(self._out, N_CLASSES)
 
     def fold(self, row: int, c: float, partners: np.ndarray) -> List[Best]:
         """55 class records over the pairs (i, row), then the records of list A and list B."""
         self.calls["fold"] += 1
         p = np.ascontiguousarray(partners, np.int32)
-        self._lib.check(self._L.hm_classmin_fold(self._h, int(row), float(c), C.c_void_p(p.ctypes.data) if len(p) else None,
-                                                 len(p), C.c_void_p(self._out.ctypes.data), self._stream()), self.eng._h)
+        self._check(self._L.hm_classmin_fold(self._h, int(row), float(c), C.c_void_p(p.ctypes.data) if len(p) else None,
+                                             len(p), C.c_void_p(self._out.ctypes.data), self._stream()))
         return _records(self._out, N_CLASSES + 2)
 
 

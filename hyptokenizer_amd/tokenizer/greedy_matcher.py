@@ -23,14 +23,13 @@ from typing import List, Optional, Sequence, Tuple
 import numpy as np
 import torch
 
+from .._handle import DeviceHandle, code_points
+
 
 def _code_points(strings: Sequence[str]) -> Tuple[np.ndarray, np.ndarray]:
-    """UTF-32 code points of ``strings`` concatenated, and int64 offsets ``[len(strings) + 1]``."""
-    offsets = np.zeros(len(strings) + 1, np.int64)
-    if strings:
-        np.cumsum([len(s) for s in strings], out=offsets[1:])
-    data = "".join(strings).encode("utf-32-le", "surrogatepass")
-    return np.frombuffer(data, dtype=np.int32).copy(), offsets
+    """Vocabulary entries, corpus lines and candidates are the caller's Python strings and may hold lone surrogates
+    (a vocabulary built by ``chr``, text decoded with ``surrogateescape``): they cross the C ABI as code points."""
+    return code_points(strings, "surrogatepass")[:2]
 
 
 class _VocabTracker:
@@ -99,43 +98,18 @@ class HostGreedyMatcher:
         return totals.astype(np.int64), (counts.astype(np.int32) if per_line else None)
 
 
-class GreedyMatcher:
+class GreedyMatcher(DeviceHandle):
     """The HIP matcher on ``device`` (a HIP device)."""
 
+    PREFIX = "hm_greedy"
+
     def __init__(self, device: torch.device):
-        from .. import _lib
-        self._lib = _lib
-        self._L = _lib.load()
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise _lib.HypMergeUnavailable(f"GreedyMatcher needs a HIP device (device={self.device})")
-        idx = self.device.index if self.device.index is not None else torch.cuda.current_device()
-        self.device = torch.device("cuda", idx)
-        h = C.c_void_p(0)
-        _lib.check(self._L.hm_greedy_create(C.byref(h), int(idx)))
-        self._h = h
+        super().__init__(device)
         self._vt = _VocabTracker()
         self._n_lines = 0
         self._n_cp = 0
         self._corpus = None            # (code points, offsets, mult): re-sent after a vocabulary rebuild
         self.last_device_ms = 0.0
-
-    def close(self) -> None:
-        if getattr(self, "_h", None) is not None and self._h.value:
-            self._L.hm_greedy_destroy(self._h)
-            self._h = C.c_void_p(0)
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def _stream(self) -> C.c_void_p:
-        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-
-    def _chk(self, st: int) -> None:
-        self._lib.check(st)
 
     def sync(self, vocab: List[str]) -> None:
         rebuild, new = self._vt.delta(vocab)
@@ -143,26 +117,23 @@ class GreedyMatcher:
             self._recreate()
         if new:
             cps, off = _code_points(new)
-            self._chk(self._L.hm_greedy_add_strings(self._h, cps.ctypes.data, off.ctypes.data, len(new), self._stream()))
+            self._check(self._L.hm_greedy_add_strings(self._h, cps.ctypes.data, off.ctypes.data, len(new), self._stream()))
 
     def _recreate(self) -> None:
         """A fresh matcher (an empty vocabulary) holding the current corpus."""
-        self.close()
-        h = C.c_void_p(0)
-        self._lib.check(self._L.hm_greedy_create(C.byref(h), int(self.device.index)))
-        self._h = h
+        self._create()
         if self._corpus is not None:
             cps, off, mult = self._corpus
-            self._chk(self._L.hm_greedy_set_corpus(self._h, cps.ctypes.data, off.ctypes.data, mult.ctypes.data,
-                                                   len(mult), self._stream()))
+            self._check(self._L.hm_greedy_set_corpus(self._h, cps.ctypes.data, off.ctypes.data, mult.ctypes.data,
+                                                     len(mult), self._stream()))
 
     def set_corpus(self, lines: Sequence[str], mult: Optional[Sequence[int]] = None) -> None:
         cps, off = _code_points(list(lines))
         mult = np.ones(len(lines), np.int64) if mult is None else np.ascontiguousarray(mult, np.int64)
         self._corpus = (cps, off, mult)
         self._n_lines, self._n_cp = len(mult), int(off[-1])
-        self._chk(self._L.hm_greedy_set_corpus(self._h, cps.ctypes.data, off.ctypes.data, mult.ctypes.data, len(mult),
-                                               self._stream()))
+        self._check(self._L.hm_greedy_set_corpus(self._h, cps.ctypes.data, off.ctypes.data, mult.ctypes.data, len(mult),
+                                                 self._stream()))
 
     def count(self, candidates: Sequence[str], per_line: bool = False):
         """-> (totals int64[K], counts int32[K, lines] or None); ``last_device_ms``: the call's time on the device."""
@@ -172,9 +143,9 @@ class GreedyMatcher:
         counts = torch.empty((max(k, 1), max(self._n_lines, 1)), dtype=torch.int32, device=self.device) if per_line else None
         start, stop = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         start.record()
-        self._chk(self._L.hm_greedy_count(self._h, cps.ctypes.data, off.ctypes.data, k,
-                                          C.c_void_p(counts.data_ptr()) if counts is not None else None,
-                                          C.c_void_p(totals.data_ptr()), self._stream()))
+        self._check(self._L.hm_greedy_count(self._h, cps.ctypes.data, off.ctypes.data, k,
+                                            C.c_void_p(counts.data_ptr()) if counts is not None else None,
+                                            C.c_void_p(totals.data_ptr()), self._stream()))
         stop.record()
         stop.synchronize()
         self.last_device_ms = start.elapsed_time(stop)
@@ -186,7 +157,7 @@ class GreedyMatcher:
         """(lm per corpus code point, base count per line) as the matcher holds them."""
         lm = torch.empty(max(self._n_cp, 1), dtype=torch.int32, device=self.device)
         base = torch.empty(max(self._n_lines, 1), dtype=torch.int32, device=self.device)
-        self._chk(self._L.hm_greedy_longest(self._h, C.c_void_p(lm.data_ptr()), C.c_void_p(base.data_ptr()), self._stream()))
+        self._check(self._L.hm_greedy_longest(self._h, C.c_void_p(lm.data_ptr()), C.c_void_p(base.data_ptr()), self._stream()))
         torch.cuda.current_stream(self.device).synchronize()
         return lm[:self._n_cp].cpu().numpy(), base[:self._n_lines].cpu().numpy()
 

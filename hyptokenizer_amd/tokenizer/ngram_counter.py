@@ -28,46 +28,21 @@ import torch
 
 from tqdm import tqdm
 
+# strict encoding: the words come out of a file read as strict UTF-8 (count_words), so they hold no lone surrogate; a
+# caller's own word list that does is refused with UnicodeEncodeError, as before
+from .._handle import DeviceHandle, code_points as words_to_code_points
+
 WORD_RE = re.compile(r"\b\w+\b")
 
 
-def words_to_code_points(words: Sequence[str]) -> Tuple[np.ndarray, np.ndarray, str]:
-    """(code points int32, offsets int64 [len(words) + 1], the joined text)."""
-    flat = "".join(words)
-    cps = np.frombuffer(flat.encode("utf-32-le"), dtype=np.int32) if flat else np.zeros(0, np.int32)
-    lens = np.fromiter(map(len, words), dtype=np.int64, count=len(words))
-    offsets = np.zeros(len(words) + 1, np.int64)
-    np.cumsum(lens, out=offsets[1:])
-    return np.ascontiguousarray(cps), offsets, flat
-
-
-class NgramCounter:
+class NgramCounter(DeviceHandle):
     """One ``hm_ngram`` counter on a HIP device."""
 
+    PREFIX = "hm_ngram"
+
     def __init__(self, device: torch.device, initial_capacity: int = 0):
-        from .. import _lib
-        self._lib = _lib
-        self._L = _lib.load()
-        device = torch.device(device)
-        if device.type != "cuda":
-            raise _lib.HypMergeUnavailable(f"NgramCounter needs a HIP device (device={device})")
-        idx = device.index if device.index is not None else torch.cuda.current_device()
-        self.device = torch.device("cuda", idx)
-        h = C.c_void_p(0)
-        _lib.check(self._L.hm_ngram_create(C.byref(h), int(idx), int(initial_capacity)))
-        self._h = h
+        super().__init__(device, int(initial_capacity))
         self.recounts = 0
-
-    def close(self) -> None:
-        if getattr(self, "_h", None) is not None and self._h.value:
-            self._L.hm_ngram_destroy(self._h)
-            self._h = C.c_void_p(0)
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def count(self, cps: np.ndarray, offsets: np.ndarray, weights: Optional[np.ndarray], distinct: bool = False):
         """-> (pos int64, len int32, count int64) of every distinct n-gram (n = 2..5) of the words, in no particular order."""
@@ -76,21 +51,21 @@ class NgramCounter:
         n_words = len(offsets) - 1
         w = None if distinct else np.ascontiguousarray(weights, np.int64)
         nd = C.c_int64(0)
-        stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-        self._lib.check(self._L.hm_ngram_count(self._h, C.c_void_p(cps.ctypes.data), C.c_void_p(offsets.ctypes.data),
-                                               None if w is None else C.c_void_p(w.ctypes.data), n_words,
-                                               self._lib.NGRAM_DISTINCT if distinct else self._lib.NGRAM_WEIGHTED,
-                                               C.byref(nd), stream))
+        stream = self._stream()
+        self._check(self._L.hm_ngram_count(self._h, C.c_void_p(cps.ctypes.data), C.c_void_p(offsets.ctypes.data),
+                                           None if w is None else C.c_void_p(w.ctypes.data), n_words,
+                                           self._lib.NGRAM_DISTINCT if distinct else self._lib.NGRAM_WEIGHTED,
+                                           C.byref(nd), stream))
         m = int(nd.value)
         pos = np.empty(m, np.int64)
         ln = np.empty(m, np.int32)
         cnt = np.empty(m, np.int64)
         rc = C.c_int64(0)
         if m:
-            self._lib.check(self._L.hm_ngram_read(self._h, C.c_void_p(pos.ctypes.data), C.c_void_p(ln.ctypes.data),
-                                                  C.c_void_p(cnt.ctypes.data), m, C.byref(rc), stream))
+            self._check(self._L.hm_ngram_read(self._h, C.c_void_p(pos.ctypes.data), C.c_void_p(ln.ctypes.data),
+                                              C.c_void_p(cnt.ctypes.data), m, C.byref(rc), stream))
         else:
-            self._lib.check(self._L.hm_ngram_read(self._h, None, None, None, 0, C.byref(rc), stream))
+            self._check(self._L.hm_ngram_read(self._h, None, None, None, 0, C.byref(rc), stream))
         self.recounts = int(rc.value)
         return pos, ln, cnt
 

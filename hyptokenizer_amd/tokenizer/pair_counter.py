@@ -31,6 +31,7 @@ from typing import Dict, List, Optional, Sequence, Tuple
 import numpy as np
 import torch
 
+from .._handle import DeviceHandle
 from .hyperbolic_merge import HyperbolicTokenizer
 
 SLAB_CODE_POINTS = 1 << 26        # code points per device upload
@@ -66,36 +67,14 @@ def tokenize_customised(tok) -> bool:
     return type(tok).tokenize is not HyperbolicTokenizer.tokenize or "tokenize" in tok.__dict__
 
 
-class PairCounter:
+class PairCounter(DeviceHandle):
     """One ``hm_pairfreq`` counter on a HIP device: slabs of (symbols, offsets, lengths) in, distinct pairs out."""
 
+    PREFIX = "hm_pairfreq"
+
     def __init__(self, device: torch.device, initial_capacity: int = 0):
-        from .. import _lib
-        self._lib = _lib
-        self._L = _lib.load()
-        device = torch.device(device)
-        if device.type != "cuda":
-            raise _lib.HypMergeUnavailable(f"PairCounter needs a HIP device (device={device})")
-        idx = device.index if device.index is not None else torch.cuda.current_device()
-        self.device = torch.device("cuda", idx)
-        h = C.c_void_p(0)
-        _lib.check(self._L.hm_pairfreq_create(C.byref(h), int(idx), int(initial_capacity)))
-        self._h = h
+        super().__init__(device, int(initial_capacity))
         self.base = 0                 # flat position of the next slab's first symbol
-
-    def close(self) -> None:
-        if getattr(self, "_h", None) is not None and self._h.value:
-            self._L.hm_pairfreq_destroy(self._h)
-            self._h = C.c_void_p(0)
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def _stream(self) -> C.c_void_p:
-        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
 
     def add(self, sym: torch.Tensor, offsets: torch.Tensor, lengths: Optional[torch.Tensor] = None) -> None:
         """One slab: int32 ``sym``, int64 ``offsets[n + 1]`` (offsets[0] = 0, offsets[n] = sym.numel()), optional
@@ -105,7 +84,7 @@ class PairCounter:
         if sym.dtype != torch.int32 or offsets.dtype != torch.int64 or \
                 (lengths is not None and (lengths.dtype != torch.int32 or lengths.numel() < n_lines)):
             raise ValueError("PairCounter.add: int32 symbols, int64 offsets, int32 lengths")
-        self._lib.check(self._L.hm_pairfreq_add(
+        self._check(self._L.hm_pairfreq_add(
             self._h, C.c_void_p(sym.data_ptr() if n_pos else 0), C.c_void_p(offsets.data_ptr()),
             C.c_void_p(lengths.data_ptr()) if lengths is not None else None, n_lines, n_pos, self.base, self._stream()))
         self.base += n_pos
@@ -113,8 +92,8 @@ class PairCounter:
     def sizes(self) -> Tuple[int, int, int]:
         """(distinct pairs, total pairs, slab recounts)"""
         d, p, r = C.c_int64(0), C.c_int64(0), C.c_int64(0)
-        self._lib.check(self._L.hm_pairfreq_read(self._h, C.byref(d), C.byref(p), C.byref(r), None, None, None, 0,
-                                                 self._stream()))
+        self._check(self._L.hm_pairfreq_read(self._h, C.byref(d), C.byref(p), C.byref(r), None, None, None, 0,
+                                             self._stream()))
         return d.value, p.value, r.value
 
     def read(self) -> Tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray, int]:
@@ -124,9 +103,9 @@ class PairCounter:
         keys = torch.empty(m, dtype=torch.int64, device=self.device)
         counts = torch.empty(m, dtype=torch.int64, device=self.device)
         first = torch.empty(m, dtype=torch.int64, device=self.device)
-        self._lib.check(self._L.hm_pairfreq_read(self._h, None, None, None, C.c_void_p(keys.data_ptr()),
-                                                 C.c_void_p(counts.data_ptr()), C.c_void_p(first.data_ptr()), m,
-                                                 self._stream()))
+        self._check(self._L.hm_pairfreq_read(self._h, None, None, None, C.c_void_p(keys.data_ptr()),
+                                             C.c_void_p(counts.data_ptr()), C.c_void_p(first.data_ptr()), m,
+                                             self._stream()))
         order = torch.argsort(first[:d])
         k = keys[:d][order].cpu().numpy()
         a = ((k >> 22) & _FIELD) - _BIAS

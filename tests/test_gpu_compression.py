@@ -73,6 +73,24 @@ def test_count_on_a_100k_code_point_line_and_long_candidates():
     assert np.array_equal(c_dev, c_host) and np.array_equal(t_dev, t_host)
 
 
+def test_vocabulary_list_replaced_after_the_corpus_was_set():
+    """Another list object is loaded from scratch: the matcher makes itself a fresh library handle, re-sends the corpus it
+    holds and must then count like the host restatement given the same two lists."""
+    rng = np.random.default_rng(8)
+    first = _random_strings(rng, ALPHABET, 200, 1, 6)
+    second = _random_strings(rng, ALPHABET, 150, 1, 7) + first[:20]
+    lines = _random_strings(rng, ALPHABET, 50, 0, 300) + [""]
+    mult = rng.integers(1, 4, len(lines))
+    dev, host = _matchers(first, lines, mult)
+    for m in (dev, host):
+        m.sync(second)
+    cands = [second[int(a)] + second[int(b)] for a, b in rng.integers(0, len(second), (100, 2))] + first[150:160]
+    t_dev, c_dev = dev.count(cands, per_line=True)
+    t_host, c_host = host.count(cands, per_line=True)
+    assert np.array_equal(c_dev, c_host) and np.array_equal(t_dev, t_host)
+    assert np.array_equal(dev.longest()[0], _host_lm(second, lines))
+
+
 def _host_lm(vocab, lines):
     entries = {t for t in vocab if t}
     longest = max(map(len, entries))

@@ -109,6 +109,19 @@ def test_forced_small_table_grows_and_recounts():
     assert timing["recounts"] > 0 and len(got) > 10_000
 
 
+def test_one_slab_overflows_its_table_more_than_twice():
+    """Initial capacity 4 and ONE slab with tens of thousands of distinct pairs: the count is repeated into tables of 16, 64,
+    256, ... slots (a table of `cap` slots overflows above `cap / 2` keys) up to the size that cannot overflow."""
+    rng = np.random.default_rng(11)
+    tok = _tok(n=300)
+    lines = _random_lines(rng, np.array(tok.vocab[:300]), 200, 200, 400)
+    want, want_total = _host(tok, lines)
+    assert len(want) > 20_000
+    got, total, timing = _device(tok, lines, initial_capacity=4)
+    assert list(got.items()) == list(want.items()) and total == want_total
+    assert timing["recounts"] >= 2
+
+
 def test_enhanced_corpus_pass_gpu_equals_host(tmp_path, caplog):
     from hyptokenizer_amd.synthetic import cjk_vocab, lorentz_table
     from hyptokenizer_amd.tokenizer.enhanced_fast_hyperbolic_merge import EnhancedFastHyperbolicTokenizer

@@ -54,6 +54,34 @@ def test_ngram_counter_random(seed):
             assert counter.recounts > 0
 
 
+def test_ngram_counter_overflows_its_tables_more_than_twice():
+    """Distinct mode from 64 slots (1 024 in effect): tens of thousands of distinct n-grams and (n-gram, word) pairs, and a
+    table of `cap` slots overflows above `cap / 2` keys, so the count is repeated into 4 096, 16 384, ... slots."""
+    from hyptokenizer_amd.tokenizer.ngram_counter import NgramCounter, ngram_counts, ngram_counts_host
+    rs = np.random.RandomState(11)
+    words = _random_words(rs, 6000, list("abcde") + ["é", "\U0001D518", "\U0010FFFF", "中"], 12)
+    want = ngram_counts_host(words, None, distinct=True)
+    assert len(want) > 20_000
+    counter = NgramCounter(DEV, initial_capacity=64)
+    grams, cnt = ngram_counts(words, None, DEV, distinct=True, counter=counter)
+    assert dict(zip(grams, cnt.tolist())) == want
+    assert counter.recounts >= 2
+
+
+def test_ngram_counter_changes_mode_on_one_handle():
+    """Distinct, weighted, distinct again on one counter: the (slot, word) set is released and made anew, the tables are
+    re-sized for another word list in between."""
+    from hyptokenizer_amd.tokenizer.ngram_counter import NgramCounter, ngram_counts, ngram_counts_host
+    rs = np.random.RandomState(12)
+    alphabet = list("abcd") + ["é", "\U0001D518"]
+    counter = NgramCounter(DEV)
+    for count, distinct in ((3000, True), (20000, False), (500, True)):
+        words = _random_words(rs, count, alphabet, 10)
+        weights = rs.randint(0, 1 << 40, len(words)).astype(np.int64)
+        grams, cnt = ngram_counts(words, weights, DEV, distinct=distinct, counter=counter)
+        assert dict(zip(grams, cnt.tolist())) == ngram_counts_host(words, weights, distinct=distinct)
+
+
 def test_ngram_counter_one_long_word():
     from hyptokenizer_amd.tokenizer.ngram_counter import ngram_counts
     rs = np.random.RandomState(5)
