@@ -46,6 +46,10 @@ EXPORTED_SYMBOLS = (
     "hm_rows_minkowski_bwd", "hm_rows_distance_bwd", "hm_rows_log_map_bwd", "hm_rows_exp_map_bwd", "hm_rows_project_bwd",
     "hm_batch_distance_bwd", "hm_infonce_fwd", "hm_infonce_bwd", "hm_triplet_fwd_bwd",
     "hm_retrieval_ranks", "hm_knn", "hm_debug_retrieval_layout",
+    "hm_rows_mobius_add", "hm_rows_mobius_scalar_mul", "hm_rows_exp_map_zero", "hm_rows_log_map_zero",
+    "hm_rows_poincare_distance", "hm_rows_lorentz_to_poincare", "hm_rows_poincare_to_lorentz",
+    "hm_rows_mobius_add_bwd", "hm_rows_mobius_scalar_mul_bwd", "hm_rows_exp_map_zero_bwd", "hm_rows_log_map_zero_bwd",
+    "hm_rows_poincare_distance_bwd", "hm_rows_lorentz_to_poincare_bwd", "hm_rows_poincare_to_lorentz_bwd",
 )
 
 
@@ -169,6 +173,20 @@ def load() -> C.CDLL:
     L.hm_retrieval_ranks.argtypes = [vp, vp, i64, i64, i64, C.c_int, C.c_int, vp, vp, vp]
     L.hm_debug_retrieval_layout.argtypes = [C.c_int]
     L.hm_knn.argtypes = [vp, i64, vp, i64, i64, i64, C.c_int, f32, C.c_int, C.c_int, C.c_int, vp, vp, vp]
+    L.hm_rows_mobius_add.argtypes = [vp, vp, i64, i64, C.c_int, f32, vp, i64, vp]
+    L.hm_rows_mobius_scalar_mul.argtypes = [vp, vp, i64, i64, C.c_int, f32, vp, i64, vp]
+    L.hm_rows_exp_map_zero.argtypes = [vp, i64, i64, C.c_int, f32, vp, i64, vp]
+    L.hm_rows_log_map_zero.argtypes = [vp, i64, i64, C.c_int, f32, vp, i64, vp]
+    L.hm_rows_poincare_distance.argtypes = [vp, vp, i64, i64, C.c_int, f32, vp, vp]
+    L.hm_rows_lorentz_to_poincare.argtypes = [vp, i64, i64, C.c_int, f32, vp, i64, vp]
+    L.hm_rows_poincare_to_lorentz.argtypes = [vp, i64, i64, C.c_int, f32, C.c_int, vp, i64, vp]
+    L.hm_rows_mobius_add_bwd.argtypes = [vp, vp, vp, i64, i64, i64, C.c_int, f32, vp, vp, i64, vp]
+    L.hm_rows_mobius_scalar_mul_bwd.argtypes = [vp, vp, vp, i64, i64, i64, C.c_int, f32, vp, vp, i64, vp]
+    L.hm_rows_exp_map_zero_bwd.argtypes = [vp, vp, i64, i64, i64, C.c_int, f32, vp, i64, vp]
+    L.hm_rows_log_map_zero_bwd.argtypes = [vp, vp, i64, i64, i64, C.c_int, f32, vp, i64, vp]
+    L.hm_rows_poincare_distance_bwd.argtypes = [vp, vp, vp, i64, i64, C.c_int, f32, vp, vp, i64, vp]
+    L.hm_rows_lorentz_to_poincare_bwd.argtypes = [vp, vp, i64, i64, i64, C.c_int, f32, vp, i64, vp]
+    L.hm_rows_poincare_to_lorentz_bwd.argtypes = [vp, vp, i64, i64, i64, C.c_int, f32, C.c_int, vp, i64, vp]
     L.hm_last_scan_stats.argtypes = [vp, pf32, pi64, pi64, pi32]
     L.hm_scan_totals.argtypes = [vp, C.POINTER(C.c_double), pi64, pi64, C.c_int]
     for name in EXPORTED_SYMBOLS:

@@ -281,6 +281,47 @@ __device__ __forceinline__ void cosh_sinh_c(float x, float& ch, float& sh)
     else sh = 0.5f * (t + t / (t + 1.0f));
 }
 
+// tanh(x), structured as fdlibm s_tanhf.c on expm1_c (torch.tanh in mobius_scalar_mul / exp_map_zero of
+// embedding/poincare_ball.py:64,83).  +-inf -> +-1, NaN propagates.
+__device__ __forceinline__ float tanh_c(float x)
+{
+    if (x != x) return x;
+    const float ax = x < 0.0f ? -x : x;
+    float z;
+    if (ax < 22.0f) {
+        if (ax < 0x1p-55f) return x;
+        if (ax >= 1.0f) {
+            const float t = expm1_c(2.0f * ax);
+            z = 1.0f - 2.0f / (t + 2.0f);
+        } else {
+            const float t = expm1_c(-2.0f * ax);
+            z = -t / (t + 2.0f);
+        }
+    } else {
+        z = 1.0f;
+    }
+    return x < 0.0f ? -z : z;
+}
+
+// atanh(x), structured as fdlibm e_atanhf.c on log1p_c (torch.atanh in mobius_scalar_mul / log_map_zero / distance of
+// embedding/poincare_ball.py:64,102,126).  +-1 -> +-inf, |x| > 1 -> NaN, NaN propagates.
+__device__ __forceinline__ float atanh_c(float x)
+{
+    if (x != x) return x;
+    const float ax = x < 0.0f ? -x : x;
+    if (ax > 1.0f) return bitsf(0x7fc00000u);
+    if (ax == 1.0f) return x < 0.0f ? bitsf(0xff800000u) : bitsf(0x7f800000u);
+    if (ax < 0x1p-28f) return x;
+    float t;
+    if (ax < 0.5f) {
+        t = ax + ax;
+        t = 0.5f * log1p_c(t + (t * ax) / (1.0f - ax));
+    } else {
+        t = 0.5f * log1p_c((ax + ax) / (1.0f - ax));
+    }
+    return x < 0.0f ? -t : t;
+}
+
 // torch.clamp(u, min = 1 + 1e-8) in fp32 (the bound is exactly 1.0f); NaN propagates.
 __device__ __forceinline__ float clamp_min_one(float u)
 {

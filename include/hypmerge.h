@@ -372,6 +372,63 @@ int hm_batch_distance_bwd(const float* X_dev, int64_t n1, const float* Y_dev, in
                           int d1, float c, int sign_mode, const float* G_dev, int64_t ld_g, float* gX_dev, float* gY_dev,
                           int64_t ld_out, void* stream);
 
+/* Row-wise Poincare-ball primitives (embedding/poincare_ball.py of the reference) on device arrays [b, d] with leading
+ * dimension ld, 1 <= d <= 128; the Lorentz side of the two conversions has d + 1 columns.  Engine-independent.  Every
+ * call returns HM_E_ARG before touching the device for a NULL pointer, d out of range, a leading dimension below the row
+ * width, or a c that is not finite and > 0.  Rows are read with 16-byte accesses when d, the leading dimensions and the
+ * base addresses allow it.
+ *   hm_rows_mobius_add          : out[b, d]     = mobius_addition(x, y, c)       (:27-46)
+ *   hm_rows_mobius_scalar_mul   : out[b, d]     = mobius_scalar_mul(r, x, c)     (:49-65, r[b]: one factor per row)
+ *   hm_rows_exp_map_zero        : out[b, d]     = exp_map_zero(v, c)             (:68-84)
+ *   hm_rows_log_map_zero        : out[b, d]     = log_map_zero(x, c)             (:87-103)
+ *   hm_rows_poincare_distance   : out[b]        = distance(x, y, c)              (:106-126)
+ *   hm_rows_lorentz_to_poincare : out[b, d]     = lorentz_to_poincare(x[b, d + 1], c)   (:129-140)
+ *   hm_rows_poincare_to_lorentz : out[b, d + 1] = poincare_to_lorentz(x[b, d], c)       (:143-163 when standard == 0: as
+ *                                 shipped, x0^2 - |x_s|^2 = 1 / (4 c); standard == 1: x0 = (1 + c |x|^2) / (sqrt(c) (1 - c |x|^2)),
+ *                                 x_s = 2 x / (1 - c |x|^2), on x0^2 - |x_s|^2 = 1 / c) */
+int hm_rows_mobius_add(const float* x_dev, const float* y_dev, int64_t b, int64_t ld, int d, float c, float* out_dev,
+                       int64_t ld_out, void* stream);
+int hm_rows_mobius_scalar_mul(const float* r_dev, const float* x_dev, int64_t b, int64_t ld, int d, float c,
+                              float* out_dev, int64_t ld_out, void* stream);
+int hm_rows_exp_map_zero(const float* v_dev, int64_t b, int64_t ld, int d, float c, float* out_dev, int64_t ld_out,
+                         void* stream);
+int hm_rows_log_map_zero(const float* x_dev, int64_t b, int64_t ld, int d, float c, float* out_dev, int64_t ld_out,
+                         void* stream);
+int hm_rows_poincare_distance(const float* x_dev, const float* y_dev, int64_t b, int64_t ld, int d, float c,
+                              float* out_dev, void* stream);
+int hm_rows_lorentz_to_poincare(const float* x_dev, int64_t b, int64_t ld, int d, float c, float* out_dev,
+                                int64_t ld_out, void* stream);
+int hm_rows_poincare_to_lorentz(const float* x_dev, int64_t b, int64_t ld, int d, float c, int standard, float* out_dev,
+                                int64_t ld_out, void* stream);
+
+/* Vector-Jacobian products of the Poincare-ball primitives above (upstream gradient g with leading dimension ld_g, or one
+ * value per row for the distance; outputs with leading dimension ld_out).  Only the inputs are read: the row scalars are
+ * recomputed.  The derivative is that of the reference's torch expression as torch differentiates it: clamp(n, min = 1e-8)
+ * passes the gradient where n >= 1e-8f and gives exactly 0 below, the (n == 0) mask arithmetic of the two zero-maps is
+ * walked back term by term, the norm has gradient 0 at the zero vector, atanh' = 1 / (1 - z^2) is infinite at 1 and finite
+ * beyond.  No gradient with respect to c.
+ *   hm_rows_mobius_add_bwd          : g[b, d]     -> gx, gy        (:27-46)
+ *   hm_rows_mobius_scalar_mul_bwd   : g[b, d]     -> gr[b], gx     (:49-65)
+ *   hm_rows_exp_map_zero_bwd        : g[b, d]     -> gv            (:68-84)
+ *   hm_rows_log_map_zero_bwd        : g[b, d]     -> gx            (:87-103)
+ *   hm_rows_poincare_distance_bwd   : g[b]        -> gx, gy        (:106-126)
+ *   hm_rows_lorentz_to_poincare_bwd : g[b, d]     -> gx[b, d + 1]  (:129-140)
+ *   hm_rows_poincare_to_lorentz_bwd : g[b, d + 1] -> gx[b, d]      (:143-163, or the standard map) */
+int hm_rows_mobius_add_bwd(const float* x_dev, const float* y_dev, const float* g_dev, int64_t ld_g, int64_t b, int64_t ld,
+                           int d, float c, float* gx_dev, float* gy_dev, int64_t ld_out, void* stream);
+int hm_rows_mobius_scalar_mul_bwd(const float* r_dev, const float* x_dev, const float* g_dev, int64_t ld_g, int64_t b,
+                                  int64_t ld, int d, float c, float* gr_dev, float* gx_dev, int64_t ld_out, void* stream);
+int hm_rows_exp_map_zero_bwd(const float* v_dev, const float* g_dev, int64_t ld_g, int64_t b, int64_t ld, int d, float c,
+                             float* gv_dev, int64_t ld_out, void* stream);
+int hm_rows_log_map_zero_bwd(const float* x_dev, const float* g_dev, int64_t ld_g, int64_t b, int64_t ld, int d, float c,
+                             float* gx_dev, int64_t ld_out, void* stream);
+int hm_rows_poincare_distance_bwd(const float* x_dev, const float* y_dev, const float* g_dev, int64_t b, int64_t ld, int d,
+                                  float c, float* gx_dev, float* gy_dev, int64_t ld_out, void* stream);
+int hm_rows_lorentz_to_poincare_bwd(const float* x_dev, const float* g_dev, int64_t ld_g, int64_t b, int64_t ld, int d,
+                                    float c, float* gx_dev, int64_t ld_out, void* stream);
+int hm_rows_poincare_to_lorentz_bwd(const float* x_dev, const float* g_dev, int64_t ld_g, int64_t b, int64_t ld, int d,
+                                    float c, int standard, float* gx_dev, int64_t ld_out, void* stream);
+
 /* Fused hyperbolic InfoNCE (multimodal/contrastive_loss.py:17-61 of the reference, c = 1): S = -distance / temp between
  * z_text[n, d1] and z_img[n, d1], cross-entropy over rows and over columns against the diagonal, averaged.  The n x n
  * matrix is never stored.  n <= 65536, d1 <= 129.
