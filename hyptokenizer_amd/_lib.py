@@ -50,6 +50,8 @@ EXPORTED_SYMBOLS = (
     "hm_rows_poincare_distance", "hm_rows_lorentz_to_poincare", "hm_rows_poincare_to_lorentz",
     "hm_rows_mobius_add_bwd", "hm_rows_mobius_scalar_mul_bwd", "hm_rows_exp_map_zero_bwd", "hm_rows_log_map_zero_bwd",
     "hm_rows_poincare_distance_bwd", "hm_rows_lorentz_to_poincare_bwd", "hm_rows_poincare_to_lorentz_bwd",
+    "hm_graph_create", "hm_graph_destroy", "hm_graph_set_csr", "hm_graph_components", "hm_graph_pair_lengths",
+    "hm_graph_distance_rows", "hm_graph_last_stats",
 )
 
 
@@ -187,6 +189,13 @@ def load() -> C.CDLL:
     L.hm_rows_poincare_distance_bwd.argtypes = [vp, vp, vp, i64, i64, C.c_int, f32, vp, vp, i64, vp]
     L.hm_rows_lorentz_to_poincare_bwd.argtypes = [vp, vp, i64, i64, i64, C.c_int, f32, vp, i64, vp]
     L.hm_rows_poincare_to_lorentz_bwd.argtypes = [vp, vp, i64, i64, i64, C.c_int, f32, C.c_int, vp, i64, vp]
+    L.hm_graph_create.argtypes = [C.POINTER(vp), C.c_int]
+    L.hm_graph_destroy.argtypes = [vp]
+    L.hm_graph_set_csr.argtypes = [vp, vp, vp, i64, vp]
+    L.hm_graph_components.argtypes = [vp, vp, pi64, vp]
+    L.hm_graph_pair_lengths.argtypes = [vp, vp, vp, i64, vp, vp]
+    L.hm_graph_distance_rows.argtypes = [vp, vp, i64, vp, i64, vp, i64, vp]
+    L.hm_graph_last_stats.argtypes = [vp, pi64, pi64, pi64, pi64]
     L.hm_last_scan_stats.argtypes = [vp, pf32, pi64, pi64, pi32]
     L.hm_scan_totals.argtypes = [vp, C.POINTER(C.c_double), pi64, pi64, C.c_int]
     for name in EXPORTED_SYMBOLS:

@@ -13,6 +13,7 @@
 //   hm_greedy.hip, hm_pairfreq.hip, hm_ngram.hip   the text side: greedy longest-match counts, adjacent-pair and n-gram
 //                   histograms of a corpus; hm_classmin.hip: per-class minima of the pair distance.  These four share
 //                   hm_table.h (owning device buffer, counting table, recount loop)
+//   hm_graph.hip    connected components and bit-parallel multi-source BFS of an undirected graph (engine-free, hm_table.h's buffers)
 //   hm_hostrng.cpp  host-only: prefix of torch.randperm
 //
 // Data layout in HBM: the fp32 "scan image" img[rows_alloc][RS], RS = 4*NG + 4 (+ 4 when needed to
@@ -307,6 +308,9 @@ struct hm_engine {
 };
 
 int hm_fail(hm_engine* e, int code, const std::string& msg);
+// hm_graph.hip: default knobs of the graph component.  HM_OK: taken; HM_E_ARG: bad value; 1: not one of its knobs
+int hm_graph_default_knob(const char* name, double value, int clear);
+bool hm_graph_owns_knob(const char* name);
 
 #define HM_HIP(call)                                                                                  \
     do {                                                                                              \

@@ -82,7 +82,15 @@ extern "C" int hm_debug_set_knob(hm_engine* e, const char* name, double value)
 extern "C" int hm_debug_set_default_knob(const char* name, double value, int clear)
 {
     const std::string k = name ? name : "";
-    if (clear) { if (k.empty()) g_default_knobs.clear(); else g_default_knobs.erase(k); return HM_OK; }
+    if (clear) {
+        if (k.empty()) { g_default_knobs.clear(); return hm_graph_default_knob(nullptr, 0.0, 1); }       // all of them, in both maps
+        if (hm_graph_owns_knob(name)) return hm_graph_default_knob(name, 0.0, 1);
+        g_default_knobs.erase(k);
+        return HM_OK;
+    }
+    // the graph component keeps its own knobs (hm_graph.hip)
+    if (const int gk = hm_graph_default_knob(name, value, 0); gk <= 0)
+        return gk ? hm_fail(nullptr, gk, "hm_debug_set_default_knob: unknown knob or value out of range") : HM_OK;
     hm_engine probe;
     const int rc = hm_apply_knob(&probe, name, value);
     if (rc) return hm_fail(nullptr, rc, "hm_debug_set_default_knob: unknown knob or value out of range");

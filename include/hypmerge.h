@@ -553,6 +553,32 @@ int hm_classmin_build(hm_classmin* cm, float c, uint32_t* out, void* stream);
 int hm_classmin_fold(hm_classmin* cm, int64_t row, float c, const int32_t* partners, int64_t n_partners, uint32_t* out,
                      void* stream);
 
+/* ---- shortest-path lengths and connected components of an undirected graph (hierarchy-distortion evaluation) --------
+ * The graph is a symmetric CSR built by the caller: HOST row_ptr int64[n + 1] (row_ptr[0] = 0, non-decreasing) and col
+ * int32[nnz], 1 <= n <= 2^24, nnz < 2^31, every index in [0, n) (HM_E_ARG otherwise).  Self-loops and repeated entries are
+ * harmless, a node of degree 0 is legal.  Independent of any engine; errors through the global last-error message; every
+ * entry point synchronises `stream`.  Path lengths come from a bit-parallel multi-source BFS: the distinct sources of a
+ * call own one bit each, a node carries W 64-bit words of seen / frontier / next, and a call whose sources exceed 64 * W
+ * runs several passes; W is the largest value with 3 * n * W * 8 bytes <= 1 GiB (at least 1), and the default knob
+ * "graph_pass_words" lowers it (tests); "graph_chunk_levels" is the number of BFS levels enqueued between two reads of the
+ * device-side counters (16).
+ * Replaces: nx.shortest_path_length(graph, a, b) once per sampled pair (scripts/eval_hierarchy.py:125-136). */
+typedef struct hm_graph hm_graph;
+int hm_graph_create(hm_graph** out, int device);
+int hm_graph_destroy(hm_graph* g);
+int hm_graph_set_csr(hm_graph* g, const int64_t* row_ptr, const int32_t* col, int64_t n, void* stream);
+/* labels_dev int32[n]: the smallest node index of the node's component; *n_components (HOST, may be NULL). */
+int hm_graph_components(hm_graph* g, int32_t* labels_dev, int64_t* n_components, void* stream);
+/* HOST src[p], dst[p] -> out_dev int32[n_pairs]: edges on a shortest path, 0 where src == dst, -1 where there is none. */
+int hm_graph_pair_lengths(hm_graph* g, const int32_t* src, const int32_t* dst, int64_t n_pairs, int32_t* out_dev, void* stream);
+/* HOST src[n_src] and cols[n_cols] (cols NULL: every node, n_cols ignored) -> out_dev int16[n_src, ld]: out[s, m] = length
+ * from src[s] to cols[m], -1 where there is none.  HM_E_CAPACITY when a listed node lies more than 32767 edges away. */
+int hm_graph_distance_rows(hm_graph* g, const int32_t* src, int64_t n_src, const int32_t* cols, int64_t n_cols, int16_t* out_dev,
+                           int64_t ld, void* stream);
+/* Of the last call above: BFS levels (component iterations) that did work, kernel launches enqueued, passes, words per
+ * node (any pointer may be NULL). */
+int hm_graph_last_stats(const hm_graph* g, int64_t* levels, int64_t* launches, int64_t* passes, int64_t* words);
+
 /* Test hook: pretend the previous refresh ended on this emission cut (bits of u'); the next whole-table top-k
  * search starts from it as given and has to notice by itself when it is too tight. */
 int hm_debug_force_cut(hm_engine* e, uint32_t cut_bits, int64_t k, float c);
@@ -562,7 +588,7 @@ int hm_debug_force_cut(hm_engine* e, uint32_t cut_bits, int64_t k, float c);
  * that draws its items from a device counter) and "dyn_slots" (size of that resident grid; 0 = what the device holds), "pipeline" (0: the standard loop
  * strictly sequential), "pipeline_pairs", "pipe_fault_at", "exact_search" (1: every top-k / count through the prefilter-free
  * exact path that is otherwise the last resort of a search whose survivors fit no emission cut), "kc_even" (default knob only:
- * bf16 image rows padded to whole 16-slot k-steps).  hm_debug_set_default_knob applies to every
+ * bf16 image rows padded to whole 16-slot k-steps), and the two default knobs of the graph component above.  hm_debug_set_default_knob applies to every
  * engine created afterwards in this process (clear != 0 removes the default `name`, or all of them when name is NULL / "").
  * The shipped library reads no environment variable for these; tuning builds (-DHM_TUNING) also accept HM_TUNE_<NAME>. */
 int hm_debug_set_knob(hm_engine* e, const char* name, double value);
