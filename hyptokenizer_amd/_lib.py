@@ -26,6 +26,8 @@ PREFILTER_AUTO, PREFILTER_F32, PREFILTER_BF16 = 0, 1, 2
 LOOP_MAX_STEPS = 256
 NGRAM_WEIGHTED, NGRAM_DISTINCT = 0, 1
 CM_CODES, CM_CLASSES, CM_SLOTS = 10, 55, 57
+TOKSTATS_COUNTERS, TOKSTATS_LEN_SHIFT, TOKSTATS_MAX_LEN, TOKSTATS_TILE = 5, 8, (1 << 24) - 1, 1024
+TOKSTATS_NONWORD, TOKSTATS_MORPHEME, TOKSTATS_FIRST_WORD, TOKSTATS_LAST_WORD = 1, 2, 4, 8
 
 #: every symbol include/hypmerge.h declares (tests check that the library exports all of them)
 EXPORTED_SYMBOLS = (
@@ -51,7 +53,7 @@ EXPORTED_SYMBOLS = (
     "hm_rows_mobius_add_bwd", "hm_rows_mobius_scalar_mul_bwd", "hm_rows_exp_map_zero_bwd", "hm_rows_log_map_zero_bwd",
     "hm_rows_poincare_distance_bwd", "hm_rows_lorentz_to_poincare_bwd", "hm_rows_poincare_to_lorentz_bwd",
     "hm_graph_create", "hm_graph_destroy", "hm_graph_set_csr", "hm_graph_components", "hm_graph_pair_lengths",
-    "hm_graph_distance_rows", "hm_graph_last_stats",
+    "hm_graph_distance_rows", "hm_graph_last_stats", "hm_tokstats",
 )
 
 
@@ -115,6 +117,7 @@ def load() -> C.CDLL:
     L.hm_tokenize_table_capacity.argtypes = [i64]
     L.hm_tokenize_build_table.argtypes = [vp, vp, vp, i64, vp, i64]
     L.hm_tokenize_batch.argtypes = [vp, vp, vp, i64, vp, i64, vp, vp, vp, vp]
+    L.hm_tokstats.argtypes = [vp, vp, vp, i64, i64, vp, i64, vp, vp, vp, i64, vp]
     L.hm_greedy_create.argtypes = [C.POINTER(vp), C.c_int]
     L.hm_greedy_destroy.argtypes = [vp]
     L.hm_greedy_set_corpus.argtypes = [vp, vp, vp, vp, i64, vp]

@@ -14,6 +14,7 @@
 //                   histograms of a corpus; hm_classmin.hip: per-class minima of the pair distance.  These four share
 //                   hm_table.h (owning device buffer, counting table, recount loop)
 //   hm_graph.hip    connected components and bit-parallel multi-source BFS of an undirected graph (engine-free, hm_table.h's buffers)
+//   hm_tokstats.hip    token statistics of a tokenised corpus (engine-free; reads what hm_tokenize.hip leaves on the device)
 //   hm_hostrng.cpp  host-only: prefix of torch.randperm
 //
 // Data layout in HBM: the fp32 "scan image" img[rows_alloc][RS], RS = 4*NG + 4 (+ 4 when needed to

@@ -501,6 +501,12 @@ class HyperbolicTokenizer:
         """``[self.encode(t) for t in texts]`` in one kernel launch."""
         return self._batch_encoder().encode_batch(texts)
 
+    def corpus_statistics(self, texts: List[str]):
+        """Token, character, word-boundary, morpheme and sub-word counts of ``texts`` (tokenizer/corpus_stats.py): the
+        integers behind scripts/compare_tokenizers.py's metrics, counted on the GPU without a token reaching the host."""
+        from .corpus_stats import corpus_statistics
+        return corpus_statistics(self, texts)
+
     def decode(self, indices: List[int]) -> str:
         return "".join(self.vocab[k] for k in indices)
 

@@ -287,6 +287,44 @@ int hm_tokenize_batch(const int32_t* sym_dev, const int64_t* offsets_dev, const 
                       const uint64_t* table_dev, int64_t capacity, int32_t* out_dev, int32_t* out_len_dev,
                       int32_t* passes_dev, void* stream);
 
+/* ---- token statistics of a tokenised corpus (corpus metrics of a tokenizer) ----------------------------------
+ * The integer counts behind the reference's corpus evaluation, over the token stream exactly as hm_tokenize_batch
+ * leaves it: line l is tok_dev[offsets_dev[l] .. offsets_dev[l] + len_dev[l]) (offsets_dev[0] = 0, n_positions =
+ * offsets_dev[n_lines]); the slots behind a line's tokens, up to offsets_dev[l + 1], are never read as tokens.
+ * Replaces: the token loops of scripts/compare_tokenizers.py -- benchmark_hyperbolic_tokenizer :177-185 (tokens and their
+ * characters), evaluate_linguistic_quality :254-278 (word-boundary, morpheme and sub-word counts) and
+ * evaluate_compression_efficiency :311-320 -- and the per-line loop of scripts/benchmark_efficiency.py:58-94.
+ *
+ * attr_dev[n_sym] (n_sym <= 2^21): one word per symbol >= 0, built by the caller from the symbol's string:
+ *   bit 0  HM_TOKSTATS_NONWORD     the string contains a character that is not a word character  (re: [^\w])
+ *   bit 1  HM_TOKSTATS_MORPHEME    the string matches the reference's suffix pattern              (:250-252)
+ *   bit 2  HM_TOKSTATS_FIRST_WORD  its first character is a word character
+ *   bit 3  HM_TOKSTATS_LAST_WORD   its last character is a word character
+ *   bits 4-7 zero;  bits 8-31: its length in code points (at most HM_TOKSTATS_MAX_LEN)
+ * wordmap_dev: 0x110000 bits (34 816 words), bit cp & 31 of word cp >> 5 set when code point cp is a word character.  A
+ * negative symbol -(2 + cp) is a token of length 1 with the flags of cp; it never matches the suffix pattern.  A symbol
+ * that is neither (>= n_sym, -1, beyond the code space) counts as a token of length 0 without flags.
+ *
+ * totals_dev[HM_TOKSTATS_COUNTERS] (zeroed by the call): [0] tokens, [1] code points of the tokens, [2] tokens with a
+ * non-word character, [3] tokens matching the suffix pattern, [4] sub-word tokens: token i of a line of n tokens whose
+ * predecessor (i > 0) ends in, or whose successor (i < n - 1) starts with, a word character on the other side of a word
+ * character of its own (:276-278); neighbours never cross a line.  line_counts_dev (may be NULL): the same five counts per
+ * line, [n_lines][HM_TOKSTATS_COUNTERS], zeroed by the call.  Sums of integers: no result depends on the launch geometry.
+ * The kernel works on tiles of HM_TOKSTATS_TILE positions; max_blocks (0: four per compute unit) caps the grid (tests).
+ * HM_E_ARG (before any device is touched): a negative size, a NULL array that is needed, n_positions >= 2^40.
+ * Asynchronous on `stream`; the current device must be the one holding the arrays. */
+#define HM_TOKSTATS_COUNTERS 5
+#define HM_TOKSTATS_NONWORD 1u
+#define HM_TOKSTATS_MORPHEME 2u
+#define HM_TOKSTATS_FIRST_WORD 4u
+#define HM_TOKSTATS_LAST_WORD 8u
+#define HM_TOKSTATS_LEN_SHIFT 8
+#define HM_TOKSTATS_MAX_LEN ((1 << 24) - 1)
+#define HM_TOKSTATS_TILE 1024
+int hm_tokstats(const int32_t* tok_dev, const int64_t* offsets_dev, const int32_t* len_dev, int64_t n_lines,
+                int64_t n_positions, const uint32_t* attr_dev, int64_t n_sym, const uint32_t* wordmap_dev,
+                uint64_t* totals_dev, uint64_t* line_counts_dev, int64_t max_blocks, void* stream);
+
 /* ---- greedy longest-match counter (compression-aware scoring) -----------------------------------------------
  * Token counts of a corpus sample under "vocabulary + one candidate string" for K candidates at once, by the
  * reference's greedy rule: at position p the longest vocabulary entry that is a prefix of text[p:], else text[p].
