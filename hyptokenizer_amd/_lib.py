@@ -54,6 +54,7 @@ EXPORTED_SYMBOLS = (
     "hm_rows_poincare_distance_bwd", "hm_rows_lorentz_to_poincare_bwd", "hm_rows_poincare_to_lorentz_bwd",
     "hm_graph_create", "hm_graph_destroy", "hm_graph_set_csr", "hm_graph_components", "hm_graph_pair_lengths",
     "hm_graph_distance_rows", "hm_graph_last_stats", "hm_tokstats",
+    "hm_rsgd_step", "hm_radam_step",
 )
 
 
@@ -192,6 +193,8 @@ def load() -> C.CDLL:
     L.hm_rows_poincare_distance_bwd.argtypes = [vp, vp, vp, i64, i64, C.c_int, f32, vp, vp, i64, vp]
     L.hm_rows_lorentz_to_poincare_bwd.argtypes = [vp, vp, i64, i64, i64, C.c_int, f32, vp, i64, vp]
     L.hm_rows_poincare_to_lorentz_bwd.argtypes = [vp, vp, i64, i64, i64, C.c_int, f32, C.c_int, vp, i64, vp]
+    L.hm_rsgd_step.argtypes = [vp, i64, vp, i64, vp, i64, vp, i64, i64, C.c_int, f32, f32, f32, C.c_int, vp]
+    L.hm_radam_step.argtypes = [vp, i64, vp, i64, vp, i64, vp, vp, i64, i64, C.c_int, f32, f32, f32, f32, f32, f32, vp]
     L.hm_graph_create.argtypes = [C.POINTER(vp), C.c_int]
     L.hm_graph_destroy.argtypes = [vp]
     L.hm_graph_set_csr.argtypes = [vp, vp, vp, i64, vp]

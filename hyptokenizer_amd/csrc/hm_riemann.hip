@@ -1,0 +1,244 @@
+// hm_riemann.hip -- one fused, in-place Riemannian optimiser step (RSGD, Riemannian Adam) for rows on the unit
+// hyperboloid <x, x> = -1, <a, b> = -a0 b0 + sum_k ak bk; engine-independent like the hm_rows_* kernels.
+//
+// Layout, that of hm_poincare.hip: a row of spatial width d = d1 - 1 <= 128 is owned by a group of 16
+// (d <= 64) or 32 lanes of one wave, a lane holds the four spatial slots sub + lanes * j (coalesced 4-byte accesses: the
+// spatial part starts one column into the row, so no 16-byte form exists for it), and the time coordinate of x, g and m is
+// a per-row scalar every lane of the group carries beside its slots.  Dots are butterfly sums over the group, so every
+// lane ends with the row scalars.  Every operand row is read once and every result row written once, in place; a group
+// lives inside one wave, whose loads of a row all precede its stores in program order.  No atomics, no LDS, no workspace.
+//
+// The step (formulas fixed by DESIGN.md 5.16, not by lorentz_model.exp_map / parallel_transport / riemannian_gradient):
+//   u  = h + <x, h> x, h = (-g0, g1, ...)                               Riemannian gradient
+//   RSGD:  m+ = mu m + (1 - dampening) u, dir = m+ or u + mu m+ (Nesterov); without momentum dir = u
+//   RAdam: m+ = b1 m + (1 - b1) u, v+ = b2 v + (1 - b2) <u, u>, dir = (m+ / bc1) / (sqrt(v+ / bc2) + eps)
+//   s  = -lr dir, n = sqrt(max(<s, s>, 0)), y_s = cosh(n) x_s + (sinh(n) / n) s_s (factor 1 at n = 0),
+//   y0 = sqrt(1 + |y_s|^2)                                              retraction, time coordinate recomputed
+//   w  = m+ + <y, m+> / (1 - <x, y>) (x + y), m' = w + <y, w> y         transport and re-projection
+#include "hm_common.h"
+
+#pragma clang fp contract(off)
+
+#define HM_RO_MAX_D 128
+#define HM_RO_THREADS 256
+#define HM_RO_SGD 0                                           // RSGD without momentum: no state
+#define HM_RO_SGD_MOM 1
+#define HM_RO_ADAM 2
+
+struct RoArgs {
+    float* x;
+    const float* g;
+    float* m;
+    float* v;
+    const int64_t* rows;
+    int64_t ld_x, ld_g, ld_m, n, table_rows;
+    int d, lsh, nesterov;
+    float lr, k_m, k_u;                                       // m+ = k_m m + k_u u: (mu, 1 - dampening) or (b1, 1 - b1)
+    float b2, omb2, eps, bc1, bc2;
+};
+
+struct RoMap {
+    int sub, lsh;
+    int64_t t, row;                                           // row t of g, row `row` of x, m, v
+    bool live;
+};
+
+__device__ __forceinline__ RoMap ro_map(const RoArgs& a)
+{
+    RoMap m;
+    const int64_t gl = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    m.lsh = a.lsh;
+    m.sub = (int)(threadIdx.x & ((1u << a.lsh) - 1u));
+    m.t = gl >> a.lsh;
+    m.row = m.t;
+    m.live = m.t < a.n;                                       // dead rows keep the origin and zeros and take part in the butterflies only
+    if (m.live && a.rows) {
+        m.row = a.rows[m.t];
+        m.live = m.row >= 0 && m.row < a.table_rows;          // an index outside the table is skipped: it never writes
+    }
+    return m;
+}
+
+// spatial part (columns 1 .. d) of row `row` of p[., ld] into the lane's slots, slots past d are 0; returns column 0
+__device__ __forceinline__ float ro_load(const float* __restrict__ p, int64_t ld, int64_t row, int d, const RoMap& m, float (&v)[4], float dead0)
+{
+#pragma unroll
+    for (int j = 0; j < 4; ++j) v[j] = 0.0f;
+    if (!m.live) return dead0;
+    const float* r = p + row * ld;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int k = m.sub + (j << m.lsh);
+        if (k < d) v[j] = r[1 + k];
+    }
+    return r[0];
+}
+
+__device__ __forceinline__ void ro_store(float* __restrict__ p, int64_t ld, int64_t row, int d, const RoMap& m, float v0, const float (&v)[4])
+{
+    if (!m.live) return;
+    float* r = p + row * ld;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int k = m.sub + (j << m.lsh);
+        if (k < d) r[1 + k] = v[j];
+    }
+    if (m.sub == 0) r[0] = v0;
+}
+
+__device__ __forceinline__ float ro_sum(const RoMap& m, float a)
+{
+    for (int off = (1 << m.lsh) >> 1; off > 0; off >>= 1) a = a + __shfl_xor(a, off, 64);
+    return a;
+}
+
+__device__ __forceinline__ float ro_sdot(const RoMap& m, const float (&a)[4], const float (&b)[4])
+{
+    return ro_sum(m, (a[0] * b[0] + a[1] * b[1]) + (a[2] * b[2] + a[3] * b[3]));
+}
+
+// <a, b> = -a0 b0 + sum_k ak bk
+__device__ __forceinline__ float ro_ldot(const RoMap& m, float a0, const float (&a)[4], float b0, const float (&b)[4])
+{
+    return ro_sdot(m, a, b) - a0 * b0;
+}
+
+template <int OPT>
+__global__ __launch_bounds__(HM_RO_THREADS) void hm_ro_step_kernel(const RoArgs a)
+{
+    const RoMap q = ro_map(a);
+    const int d = a.d;
+    float xs[4], gs[4], ms[4], us[4], ss[4], ys[4], ws[4];
+    const float x0 = ro_load(a.x, a.ld_x, q.row, d, q, xs, 1.0f);
+    const float g0 = ro_load(a.g, a.ld_g, q.t, d, q, gs, 0.0f);
+    float m0 = 0.0f, vv = 0.0f;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) ms[j] = 0.0f;
+    if (OPT != HM_RO_SGD) m0 = ro_load(a.m, a.ld_m, q.row, d, q, ms, 0.0f);
+    if (OPT == HM_RO_ADAM && q.live) vv = a.v[q.row];
+
+    // Riemannian gradient: h = (-g0, g_s), u = h + <x, h> x
+    const float h0 = -g0;
+    const float xh = ro_ldot(q, x0, xs, h0, gs);
+    const float u0 = h0 + xh * x0;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) us[j] = gs[j] + xh * xs[j];
+
+    // moments and direction; s = -lr dir
+    float s0;
+    if (OPT == HM_RO_SGD) {
+        m0 = u0;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) ms[j] = us[j];
+        s0 = -a.lr * u0;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) ss[j] = -a.lr * us[j];
+    } else if (OPT == HM_RO_SGD_MOM) {
+        m0 = a.k_m * m0 + a.k_u * u0;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) ms[j] = a.k_m * ms[j] + a.k_u * us[j];
+        if (a.nesterov) {
+            s0 = -a.lr * (u0 + a.k_m * m0);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) ss[j] = -a.lr * (us[j] + a.k_m * ms[j]);
+        } else {
+            s0 = -a.lr * m0;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) ss[j] = -a.lr * ms[j];
+        }
+    } else {
+        m0 = a.k_m * m0 + a.k_u * u0;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) ms[j] = a.k_m * ms[j] + a.k_u * us[j];
+        const float uu = ro_ldot(q, u0, us, u0, us);          // the row's squared Riemannian norm
+        vv = a.b2 * vv + a.omb2 * uu;
+        const float den = __builtin_sqrtf(vv / a.bc2) + a.eps;
+        s0 = -a.lr * ((m0 / a.bc1) / den);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) ss[j] = -a.lr * ((ms[j] / a.bc1) / den);
+    }
+
+    // retraction: Exp_x(s), then the time coordinate from the spatial part
+    const float n2 = ro_ldot(q, s0, ss, s0, ss);
+    const float nn = __builtin_sqrtf((n2 < 0.0f) ? 0.0f : n2);   // NaN propagates
+    float ch, sh;
+    hm::cosh_sinh_c(nn, ch, sh);
+    const float coef = (nn > 0.0f) ? sh / nn : 1.0f;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) ys[j] = ch * xs[j] + coef * ss[j];
+    const float y0 = __builtin_sqrtf(1.0f + ro_sdot(q, ys, ys));
+    ro_store(a.x, a.ld_x, q.row, d, q, y0, ys);
+    if (OPT == HM_RO_SGD) return;
+
+    // transport of m+ from x to y, re-projected onto the tangent space at y
+    const float ym = ro_ldot(q, y0, ys, m0, ms);
+    const float xy = ro_ldot(q, x0, xs, y0, ys);
+    const float f = ym / (1.0f - xy);
+    const float w0 = m0 + f * (x0 + y0);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) ws[j] = ms[j] + f * (xs[j] + ys[j]);
+    const float yw = ro_ldot(q, y0, ys, w0, ws);
+    const float o0 = w0 + yw * y0;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) ws[j] = ws[j] + yw * ys[j];
+    ro_store(a.m, a.ld_m, q.row, d, q, o0, ws);
+    if (OPT == HM_RO_ADAM && q.live && q.sub == 0) a.v[q.row] = vv;
+}
+
+// ------------------------------------------------------------------------------------------------
+// C ABI
+// ------------------------------------------------------------------------------------------------
+static inline bool ro_unit(float b) { return b >= 0.0f && b < 1.0f; }            // false for NaN
+static inline bool ro_bad_common(int64_t ld_x, int64_t ld_g, int64_t n, int64_t table_rows, int d1, float lr, bool dense)
+{
+    if (d1 < 2 || d1 > HM_RO_MAX_D + 1 || ld_x < d1 || ld_g < d1) return true;
+    if (n < 0 || n > ((int64_t)1 << 31) || table_rows < 0 || (dense && n != table_rows)) return true;
+    return !(lr >= 0.0f) || !(lr < INFINITY);
+}
+
+template <int OPT>
+static int ro_launch(const RoArgs& a, void* stream)
+{
+    const unsigned grid = (unsigned)(((a.n << a.lsh) + HM_RO_THREADS - 1) / HM_RO_THREADS);
+    hipLaunchKernelGGL(hm_ro_step_kernel<OPT>, dim3(grid), dim3(HM_RO_THREADS), 0, (hipStream_t)stream, a);
+    HM_HIP0(hipGetLastError());
+    return HM_OK;
+}
+
+extern "C" int hm_rsgd_step(float* x_dev, int64_t ld_x, const float* g_dev, int64_t ld_g, float* m_dev, int64_t ld_m,
+                            const int64_t* rows_dev, int64_t n, int64_t table_rows, int d1, float lr, float momentum, float dampening,
+                            int nesterov, void* stream)
+{
+    if (ro_bad_common(ld_x, ld_g, n, table_rows, d1, lr, rows_dev == nullptr) || !ro_unit(momentum) || !ro_unit(dampening) ||
+        (nesterov != 0 && nesterov != 1))
+        return hm_fail(nullptr, HM_E_ARG, "hm_rsgd_step: bad arguments");
+    if (!x_dev || !g_dev) return hm_fail(nullptr, HM_E_ARG, "hm_rsgd_step: NULL pointer");
+    const bool mom = momentum != 0.0f;
+    if (mom != (m_dev != nullptr)) return hm_fail(nullptr, HM_E_ARG, "hm_rsgd_step: the momentum buffer is given exactly when momentum != 0");
+    if (mom && ld_m < d1) return hm_fail(nullptr, HM_E_ARG, "hm_rsgd_step: bad arguments");
+    if (n == 0) return HM_OK;
+    RoArgs a = {};
+    a.x = x_dev; a.g = g_dev; a.m = m_dev; a.rows = rows_dev;
+    a.ld_x = ld_x; a.ld_g = ld_g; a.ld_m = ld_m; a.n = n; a.table_rows = table_rows;
+    a.d = d1 - 1; a.lsh = (a.d <= 64) ? 4 : 5; a.nesterov = nesterov;
+    a.lr = lr; a.k_m = momentum; a.k_u = (float)(1.0 - (double)dampening);
+    return mom ? ro_launch<HM_RO_SGD_MOM>(a, stream) : ro_launch<HM_RO_SGD>(a, stream);
+}
+
+extern "C" int hm_radam_step(float* x_dev, int64_t ld_x, const float* g_dev, int64_t ld_g, float* m_dev, int64_t ld_m, float* v_dev,
+                             const int64_t* rows_dev, int64_t n, int64_t table_rows, int d1, float lr, float beta1, float beta2,
+                             float eps, float bc1, float bc2, void* stream)
+{
+    if (ro_bad_common(ld_x, ld_g, n, table_rows, d1, lr, rows_dev == nullptr) || ld_m < d1 || !ro_unit(beta1) || !ro_unit(beta2) ||
+        !(bc1 > 0.0f) || !(bc1 < INFINITY) || !(bc2 > 0.0f) || !(bc2 < INFINITY) || !(eps >= 0.0f) || !(eps < INFINITY))
+        return hm_fail(nullptr, HM_E_ARG, "hm_radam_step: bad arguments");
+    if (!x_dev || !g_dev || !m_dev || !v_dev) return hm_fail(nullptr, HM_E_ARG, "hm_radam_step: NULL pointer");
+    if (n == 0) return HM_OK;
+    RoArgs a = {};
+    a.x = x_dev; a.g = g_dev; a.m = m_dev; a.v = v_dev; a.rows = rows_dev;
+    a.ld_x = ld_x; a.ld_g = ld_g; a.ld_m = ld_m; a.n = n; a.table_rows = table_rows;
+    a.d = d1 - 1; a.lsh = (a.d <= 64) ? 4 : 5;
+    a.lr = lr; a.k_m = beta1; a.k_u = (float)(1.0 - (double)beta1);
+    a.b2 = beta2; a.omb2 = (float)(1.0 - (double)beta2); a.eps = eps; a.bc1 = bc1; a.bc2 = bc2;
+    return ro_launch<HM_RO_ADAM>(a, stream);
+}

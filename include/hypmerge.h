@@ -617,6 +617,29 @@ int hm_graph_distance_rows(hm_graph* g, const int32_t* src, int64_t n_src, const
  * node (any pointer may be NULL). */
 int hm_graph_last_stats(const hm_graph* g, int64_t* levels, int64_t* launches, int64_t* passes, int64_t* words);
 
+/* ---- Riemannian optimiser steps for rows on the unit hyperboloid -----------------------------------
+ * One fused, in-place step per call: x [table_rows, ld_x] holds points with <x, x> = -1 under <a, b> = -a0 b0 + sum ak bk
+ * (d1 = d + 1 columns, 2 <= d1 <= 129), g the Euclidean gradient of a loss with respect to them, m the first moment
+ * (tangent at x, transported to the new point), v (RAdam) one second moment per row.  Curvature only scales distances
+ * and is folded into lr by the caller.
+ *   dense   (rows_dev NULL, n == table_rows): row t of g updates row t of x, m, v;
+ *   indexed (rows_dev int64[n] on the device): row t of the compact g [n, ld_g] updates row rows_dev[t] of x, m, v; an
+ *           index outside [0, table_rows) is skipped (nothing is written for it), indices must be distinct.
+ * hm_rsgd_step:  m+ = momentum m + (1 - dampening) u, step along m+ (nesterov: u + momentum m+); with momentum == 0
+ *                m_dev must be NULL, dampening is ignored and the step is along u.
+ * hm_radam_step: m+ = beta1 m + (1 - beta1) u, v+ = beta2 v + (1 - beta2) <u, u>, step along (m+ / bc1) / (sqrt(v+ / bc2) + eps);
+ *                bc1 = 1 - beta1^t and bc2 = 1 - beta2^t come from the caller (nothing is read back from the device).
+ * Engine-independent; errors through hm_last_error(NULL); asynchronous on `stream`.  HM_E_ARG before the device is touched
+ * for a NULL required pointer, d1 outside 2..129, a leading dimension below d1, n < 0 (or != table_rows in the dense
+ * form), lr negative or not finite, momentum / dampening / beta outside [0, 1), bc <= 0, eps < 0.  n == 0: HM_OK, no launch.
+ * Replaces: nothing the reference runs -- its riemannian_gradient / exp_map / parallel_transport (lorentz_model.py) are
+ * never called and do not compose into a step that stays on the hyperboloid. */
+int hm_rsgd_step(float* x_dev, int64_t ld_x, const float* g_dev, int64_t ld_g, float* m_dev, int64_t ld_m, const int64_t* rows_dev,
+                 int64_t n, int64_t table_rows, int d1, float lr, float momentum, float dampening, int nesterov, void* stream);
+int hm_radam_step(float* x_dev, int64_t ld_x, const float* g_dev, int64_t ld_g, float* m_dev, int64_t ld_m, float* v_dev,
+                  const int64_t* rows_dev, int64_t n, int64_t table_rows, int d1, float lr, float beta1, float beta2, float eps,
+                  float bc1, float bc2, void* stream);
+
 /* Test hook: pretend the previous refresh ended on this emission cut (bits of u'); the next whole-table top-k
  * search starts from it as given and has to notice by itself when it is too tight. */
 int hm_debug_force_cut(hm_engine* e, uint32_t cut_bits, int64_t k, float c);
