@@ -3,11 +3,13 @@
 //   hm_engine.hip   engine lifetime, table upload, statistics            (host)
 //   hm_scan.hip     the pair-scan kernel (MFMA prefilter) and its launch  (hot kernel)
 //   hm_search.hip   exact re-evaluation / selection kernels and the search entry points of the ABI
-//   hm_rows.hip     image construction, merge / midpoint, one-row-vs-all, gathered and row-wise kernels
+//   hm_rows.hip     the engine's row work: image construction, merge / midpoint, one-row-vs-all and gathered distances
 //   hm_loops.hip    device-resident merge loops (several steps per host call)
 //   hm_exact.hip    the prefilter-free search, last resort of the top-k search
 //   hm_comm.hip     the row-sharded search with its exchange step inside the library (RCCL)
-//   hm_rowgrad.hip, hm_contrastive.hip   backward kernels of the row-wise primitives; fused InfoNCE / triplet loss
+//   hm_lorentz.hip  the row-wise Lorentz primitives, forward and backward (engine-free, like everything below)
+//   hm_poincare.hip, hm_riemann.hip   Poincare-ball primitives; fused Riemannian optimiser steps (lane groups of hm_rowgroup.h)
+//   hm_contrastive.hip   fused InfoNCE / triplet loss
 //   hm_retrieval.hip   recall@K ranks and exact k nearest keys
 //   hm_tokenize.hip    batch form of HyperbolicTokenizer.tokenize (engine-free, like the four below)
 //   hm_greedy.hip, hm_pairfreq.hip, hm_ngram.hip   the text side: greedy longest-match counts, adjacent-pair and n-gram

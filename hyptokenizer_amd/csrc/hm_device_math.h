@@ -335,4 +335,39 @@ __device__ __forceinline__ float dist_from_u(float u, float sqrt_c)
     return acosh_c(clamp_min_one(u)) / sqrt_c;
 }
 
+// ---- the scalars of the Lorentz row primitives (embedding/lorentz_model.py), each written once for the midpoint, the
+// forward row kernels and the backward row kernels ----
+#define HM_LOG_COEF_MAX 1.0e4f       // log_map: clamp(coef, max = 1e4)
+#define HM_EXP_N2_MIN 1.0e-8f        // exp_map: clamp(|v_s|^2, min = 1e-8)
+
+// log_map (:96-119): the factor of y + <x, y> x from u.  a = clamp(u, min = 1), A = acosh(a), Q = sqrt(a * a - 1),
+// coef0 = A / Q, coef = clamp(coef0, max = 1e4) with NaN kept.  The backward kernel needs the intermediates as well.
+struct LogMapCoef { float a, A, Q, coef0, coef; };
+
+__device__ __forceinline__ LogMapCoef log_map_coef(float u)
+{
+    LogMapCoef r;
+    r.a = clamp_min_one(u);
+    r.A = acosh_c(r.a);
+    r.Q = __builtin_sqrtf(r.a * r.a - 1.0f);
+    r.coef0 = r.A / r.Q;
+    r.coef = r.coef0;
+    if (r.coef == r.coef && r.coef > HM_LOG_COEF_MAX) r.coef = HM_LOG_COEF_MAX;
+    return r;
+}
+
+// exp_map (:73-93): the tangent's norm from its squared spatial norm, clamped below; NaN propagates.
+__device__ __forceinline__ float exp_map_norm(float n2)
+{
+    if (n2 == n2 && n2 < HM_EXP_N2_MIN) n2 = HM_EXP_N2_MIN;
+    return __builtin_sqrtf(n2);
+}
+
+// project_to_hyperboloid (:41-56): the time coordinate from the squared spatial norm.
+__device__ __forceinline__ float project_x0(float r2, float c)
+{
+    const float rr = __builtin_sqrtf(r2);
+    return __builtin_sqrtf(1.0f + (c * rr) * rr);
+}
+
 }  // namespace hm

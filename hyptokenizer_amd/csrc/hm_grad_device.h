@@ -1,4 +1,4 @@
-// hm_grad_device.h -- device helpers shared by the backward kernels (hm_rowgrad.hip, hm_contrastive.hip).
+// hm_grad_device.h -- device helpers shared by the Lorentz row kernels and the backward kernels (hm_lorentz.hip, hm_contrastive.hip).
 //
 // Derivative conventions: what is differentiated is the reference's torch expression as torch
 // differentiates it, not the ideal function.

@@ -1,12 +1,11 @@
 // hm_riemann.hip -- one fused, in-place Riemannian optimiser step (RSGD, Riemannian Adam) for rows on the unit
 // hyperboloid <x, x> = -1, <a, b> = -a0 b0 + sum_k ak bk; engine-independent like the hm_rows_* kernels.
 //
-// Layout, that of hm_poincare.hip: a row of spatial width d = d1 - 1 <= 128 is owned by a group of 16
-// (d <= 64) or 32 lanes of one wave, a lane holds the four spatial slots sub + lanes * j (coalesced 4-byte accesses: the
-// spatial part starts one column into the row, so no 16-byte form exists for it), and the time coordinate of x, g and m is
-// a per-row scalar every lane of the group carries beside its slots.  Dots are butterfly sums over the group, so every
-// lane ends with the row scalars.  Every operand row is read once and every result row written once, in place; a group
-// lives inside one wave, whose loads of a row all precede its stores in program order.  No atomics, no LDS, no workspace.
+// Layout: the lane groups of hm_rowgroup.h, a group per row of spatial width d = d1 - 1 <= 128, always in
+// the scalar form (the spatial part starts one column into the row, so no 16-byte form exists for it).  The time coordinate
+// of x, g and m is a per-row scalar every lane of the group carries beside its slots.  Every operand row is read once and
+// every result row written once, in place; a group lives inside one wave, whose loads of a row all precede its stores in
+// program order.  No atomics, no LDS, no workspace.
 //
 // The step (formulas fixed by DESIGN.md 5.16, not by lorentz_model.exp_map / parallel_transport / riemannian_gradient):
 //   u  = h + <x, h> x, h = (-g0, g1, ...)                               Riemannian gradient
@@ -15,12 +14,10 @@
 //   s  = -lr dir, n = sqrt(max(<s, s>, 0)), y_s = cosh(n) x_s + (sinh(n) / n) s_s (factor 1 at n = 0),
 //   y0 = sqrt(1 + |y_s|^2)                                              retraction, time coordinate recomputed
 //   w  = m+ + <y, m+> / (1 - <x, y>) (x + y), m' = w + <y, w> y         transport and re-projection
-#include "hm_common.h"
+#include "hm_rowgroup.h"
 
 #pragma clang fp contract(off)
 
-#define HM_RO_MAX_D 128
-#define HM_RO_THREADS 256
 #define HM_RO_SGD 0                                           // RSGD without momentum: no state
 #define HM_RO_SGD_MOM 1
 #define HM_RO_ADAM 2
@@ -37,85 +34,48 @@ struct RoArgs {
     float b2, omb2, eps, bc1, bc2;
 };
 
-struct RoMap {
-    int sub, lsh;
-    int64_t t, row;                                           // row t of g, row `row` of x, m, v
-    bool live;
-};
-
-__device__ __forceinline__ RoMap ro_map(const RoArgs& a)
+// column 0 of a Lorentz row beside its slots: read by every lane of a live group, written by the group's first lane
+__device__ __forceinline__ float ro_time(const float* __restrict__ r, const RgMap& q, float dead0) { return q.live ? r[0] : dead0; }
+__device__ __forceinline__ void ro_set_time(float* __restrict__ r, const RgMap& q, float v0)
 {
-    RoMap m;
-    const int64_t gl = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    m.lsh = a.lsh;
-    m.sub = (int)(threadIdx.x & ((1u << a.lsh) - 1u));
-    m.t = gl >> a.lsh;
-    m.row = m.t;
-    m.live = m.t < a.n;                                       // dead rows keep the origin and zeros and take part in the butterflies only
-    if (m.live && a.rows) {
-        m.row = a.rows[m.t];
-        m.live = m.row >= 0 && m.row < a.table_rows;          // an index outside the table is skipped: it never writes
-    }
-    return m;
-}
-
-// spatial part (columns 1 .. d) of row `row` of p[., ld] into the lane's slots, slots past d are 0; returns column 0
-__device__ __forceinline__ float ro_load(const float* __restrict__ p, int64_t ld, int64_t row, int d, const RoMap& m, float (&v)[4], float dead0)
-{
-#pragma unroll
-    for (int j = 0; j < 4; ++j) v[j] = 0.0f;
-    if (!m.live) return dead0;
-    const float* r = p + row * ld;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const int k = m.sub + (j << m.lsh);
-        if (k < d) v[j] = r[1 + k];
-    }
-    return r[0];
-}
-
-__device__ __forceinline__ void ro_store(float* __restrict__ p, int64_t ld, int64_t row, int d, const RoMap& m, float v0, const float (&v)[4])
-{
-    if (!m.live) return;
-    float* r = p + row * ld;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const int k = m.sub + (j << m.lsh);
-        if (k < d) r[1 + k] = v[j];
-    }
-    if (m.sub == 0) r[0] = v0;
-}
-
-__device__ __forceinline__ float ro_sum(const RoMap& m, float a)
-{
-    for (int off = (1 << m.lsh) >> 1; off > 0; off >>= 1) a = a + __shfl_xor(a, off, 64);
-    return a;
-}
-
-__device__ __forceinline__ float ro_sdot(const RoMap& m, const float (&a)[4], const float (&b)[4])
-{
-    return ro_sum(m, (a[0] * b[0] + a[1] * b[1]) + (a[2] * b[2] + a[3] * b[3]));
+    if (q.live && q.sub == 0) r[0] = v0;
 }
 
 // <a, b> = -a0 b0 + sum_k ak bk
-__device__ __forceinline__ float ro_ldot(const RoMap& m, float a0, const float (&a)[4], float b0, const float (&b)[4])
+__device__ __forceinline__ float ro_ldot(const RgMap& m, float a0, const float (&a)[4], float b0, const float (&b)[4])
 {
-    return ro_sdot(m, a, b) - a0 * b0;
+    return rg_dot(m, a, b) - a0 * b0;
 }
 
 template <int OPT>
-__global__ __launch_bounds__(HM_RO_THREADS) void hm_ro_step_kernel(const RoArgs a)
+__global__ __launch_bounds__(HM_RG_THREADS) void hm_ro_step_kernel(const RoArgs a)
 {
-    const RoMap q = ro_map(a);
+    // group t steps gradient row t; its x, m and v rows are row t of the table, or row rows[t] when indexed.  An index
+    // outside the table is not live: it never writes
+    RgMap q = rg_map(a.lsh, 0, a.n);
+    const int64_t t = q.row;
+    int64_t row = t;
+    if (q.live && a.rows) {
+        row = a.rows[t];
+        q.live = row >= 0 && row < a.table_rows;
+    }
     const int d = a.d;
+    float* xr = a.x + row * a.ld_x;
+    const float* gr = a.g + t * a.ld_g;
+    float* mr = a.m + row * a.ld_m;
     float xs[4], gs[4], ms[4], us[4], ss[4], ys[4], ws[4];
-    const float x0 = ro_load(a.x, a.ld_x, q.row, d, q, xs, 1.0f);
-    const float g0 = ro_load(a.g, a.ld_g, q.t, d, q, gs, 0.0f);
+    const float x0 = ro_time(xr, q, 1.0f);                    // dead rows keep the origin
+    rg_load(xr + 1, d, q, xs);
+    const float g0 = ro_time(gr, q, 0.0f);
+    rg_load(gr + 1, d, q, gs);
     float m0 = 0.0f, vv = 0.0f;
 #pragma unroll
     for (int j = 0; j < 4; ++j) ms[j] = 0.0f;
-    if (OPT != HM_RO_SGD) m0 = ro_load(a.m, a.ld_m, q.row, d, q, ms, 0.0f);
-    if (OPT == HM_RO_ADAM && q.live) vv = a.v[q.row];
+    if (OPT != HM_RO_SGD) {
+        m0 = ro_time(mr, q, 0.0f);
+        rg_load(mr + 1, d, q, ms);
+    }
+    if (OPT == HM_RO_ADAM && q.live) vv = a.v[row];
 
     // Riemannian gradient: h = (-g0, g_s), u = h + <x, h> x
     const float h0 = -g0;
@@ -166,8 +126,9 @@ __global__ __launch_bounds__(HM_RO_THREADS) void hm_ro_step_kernel(const RoArgs 
     const float coef = (nn > 0.0f) ? sh / nn : 1.0f;
 #pragma unroll
     for (int j = 0; j < 4; ++j) ys[j] = ch * xs[j] + coef * ss[j];
-    const float y0 = __builtin_sqrtf(1.0f + ro_sdot(q, ys, ys));
-    ro_store(a.x, a.ld_x, q.row, d, q, y0, ys);
+    const float y0 = __builtin_sqrtf(1.0f + rg_dot(q, ys, ys));
+    rg_store(xr + 1, d, q, ys);
+    ro_set_time(xr, q, y0);
     if (OPT == HM_RO_SGD) return;
 
     // transport of m+ from x to y, re-projected onto the tangent space at y
@@ -181,8 +142,9 @@ __global__ __launch_bounds__(HM_RO_THREADS) void hm_ro_step_kernel(const RoArgs 
     const float o0 = w0 + yw * y0;
 #pragma unroll
     for (int j = 0; j < 4; ++j) ws[j] = ws[j] + yw * ys[j];
-    ro_store(a.m, a.ld_m, q.row, d, q, o0, ws);
-    if (OPT == HM_RO_ADAM && q.live && q.sub == 0) a.v[q.row] = vv;
+    rg_store(mr + 1, d, q, ws);
+    ro_set_time(mr, q, o0);
+    if (OPT == HM_RO_ADAM && q.live && q.sub == 0) a.v[row] = vv;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -191,7 +153,7 @@ __global__ __launch_bounds__(HM_RO_THREADS) void hm_ro_step_kernel(const RoArgs 
 static inline bool ro_unit(float b) { return b >= 0.0f && b < 1.0f; }            // false for NaN
 static inline bool ro_bad_common(int64_t ld_x, int64_t ld_g, int64_t n, int64_t table_rows, int d1, float lr, bool dense)
 {
-    if (d1 < 2 || d1 > HM_RO_MAX_D + 1 || ld_x < d1 || ld_g < d1) return true;
+    if (d1 < 2 || d1 > HM_RG_MAX_D + 1 || ld_x < d1 || ld_g < d1) return true;
     if (n < 0 || n > ((int64_t)1 << 31) || table_rows < 0 || (dense && n != table_rows)) return true;
     return !(lr >= 0.0f) || !(lr < INFINITY);
 }
@@ -199,8 +161,7 @@ static inline bool ro_bad_common(int64_t ld_x, int64_t ld_g, int64_t n, int64_t 
 template <int OPT>
 static int ro_launch(const RoArgs& a, void* stream)
 {
-    const unsigned grid = (unsigned)(((a.n << a.lsh) + HM_RO_THREADS - 1) / HM_RO_THREADS);
-    hipLaunchKernelGGL(hm_ro_step_kernel<OPT>, dim3(grid), dim3(HM_RO_THREADS), 0, (hipStream_t)stream, a);
+    hipLaunchKernelGGL(hm_ro_step_kernel<OPT>, rg_grid(a.n, a.lsh), dim3(HM_RG_THREADS), 0, (hipStream_t)stream, a);
     HM_HIP0(hipGetLastError());
     return HM_OK;
 }
@@ -220,7 +181,7 @@ extern "C" int hm_rsgd_step(float* x_dev, int64_t ld_x, const float* g_dev, int6
     RoArgs a = {};
     a.x = x_dev; a.g = g_dev; a.m = m_dev; a.rows = rows_dev;
     a.ld_x = ld_x; a.ld_g = ld_g; a.ld_m = ld_m; a.n = n; a.table_rows = table_rows;
-    a.d = d1 - 1; a.lsh = (a.d <= 64) ? 4 : 5; a.nesterov = nesterov;
+    a.d = d1 - 1; a.lsh = rg_lsh(a.d); a.nesterov = nesterov;
     a.lr = lr; a.k_m = momentum; a.k_u = (float)(1.0 - (double)dampening);
     return mom ? ro_launch<HM_RO_SGD_MOM>(a, stream) : ro_launch<HM_RO_SGD>(a, stream);
 }
@@ -237,7 +198,7 @@ extern "C" int hm_radam_step(float* x_dev, int64_t ld_x, const float* g_dev, int
     RoArgs a = {};
     a.x = x_dev; a.g = g_dev; a.m = m_dev; a.v = v_dev; a.rows = rows_dev;
     a.ld_x = ld_x; a.ld_g = ld_g; a.ld_m = ld_m; a.n = n; a.table_rows = table_rows;
-    a.d = d1 - 1; a.lsh = (a.d <= 64) ? 4 : 5;
+    a.d = d1 - 1; a.lsh = rg_lsh(a.d);
     a.lr = lr; a.k_m = beta1; a.k_u = (float)(1.0 - (double)beta1);
     a.b2 = beta2; a.omb2 = (float)(1.0 - (double)beta2); a.eps = eps; a.bc1 = bc1; a.bc2 = bc2;
     return ro_launch<HM_RO_ADAM>(a, stream);

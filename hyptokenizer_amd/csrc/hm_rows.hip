@@ -1,5 +1,6 @@
-// hm_rows.hip -- image construction, merge / midpoint, gathered and row-wise kernels, table re-projection and
-// the coherence kernel of the enhanced tokenizer, with their C-ABI entry points (include/hypmerge.h).
+// hm_rows.hip -- the engine's row work: image construction, merge / midpoint, gathered and one-vs-all distances, table
+// re-projection and the coherence kernel of the enhanced tokenizer, with their C-ABI entry points (include/hypmerge.h).
+// The engine-independent Lorentz row primitives are in hm_lorentz.hip.
 //
 // All of these are bandwidth / latency kernels: rows are read coalesced (a half-wave reads
 // one 128-byte segment per instruction) and every canonical reduction is done wave-cooperatively
@@ -311,8 +312,7 @@ __global__ __launch_bounds__(64) void hm_project_table_kernel(float* __restrict_
             for (int q = 0; q < 16; ++q) r2 = __builtin_fmaf(v[q], v[q], r2);
         }
         for (; k < d; ++k) r2 = __builtin_fmaf(rowp[k], rowp[k], r2);
-        const float rr = __builtin_sqrtf(r2);
-        x0 = __builtin_sqrtf(1.0f + (c * rr) * rr);
+        x0 = hm::project_x0(r2, c);
         const int64_t row = r0 + lane;
         X[row * ld] = x0;
         if (row < n_live) {
@@ -342,114 +342,6 @@ __global__ __launch_bounds__(64) void hm_project_table_kernel(float* __restrict_
         if (q2 > 0.0f) hm_raise_bits(rmax2_bits, hm::fbits(q2 * 1.0001f));
         if (r2 > 0.0f) hm_raise_bits(rmax2_bits + 1, hm::fbits(r2 * 1.0001f));
     }
-}
-
-// ------------------------------------------------------------------------------------------------
-// engine-independent kernels on row-major arrays (embedding/lorentz_model.py function surface)
-// ------------------------------------------------------------------------------------------------
-__device__ __forceinline__ float hm_rm_u(const float* x, const float* y, int d1, int sign_mode)
-{
-    const float S = hm::torch_order_sum([&](int s) { return x[1 + s] * y[1 + s]; }, d1 - 1);
-    const float t = x[0] * y[0];
-    const float m = t - S;
-    return sign_mode ? m : -m;
-}
-
-// half-wave per row pair (coalesced)
-__device__ __forceinline__ float hm_rm_u_halfwave(const float* x, const float* y, int d1, int sign_mode, int lane)
-{
-    const float S = hm_halfwave_sum(d1 - 1, lane, [&](int e) { return x[1 + e] * y[1 + e]; });
-    const float t = x[0] * y[0];
-    const float m = t - S;
-    return sign_mode ? m : -m;
-}
-
-// one half-wave per 32 consecutive outputs (row-major enumeration of out[i, j])
-__global__ __launch_bounds__(256) void hm_dense_kernel(const float* __restrict__ X, int64_t n1, const float* __restrict__ Y, int64_t n2,
-                                                       int64_t ldx, int64_t ldy, int d1, float sqrt_c, int sign_mode,
-                                                       float* __restrict__ out)
-{
-    const int lane = threadIdx.x & 63, t = lane & 31;
-    const int64_t total = n1 * n2;
-    const int64_t nhw = ((int64_t)gridDim.x * blockDim.x) >> 5;
-    const int64_t hw = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 5;
-    for (int64_t base = (hw & ~(int64_t)1) * HM_GATHER; base < total; base += nhw * HM_GATHER) {
-        const int64_t mybase = base + (hw & 1) * HM_GATHER;
-        const float u = hm_halfwave_gather(lane, [&](int k) {
-            const int64_t o = mybase + k < total ? mybase + k : total - 1;
-            const int64_t i = o / n2, j = o - i * n2;
-            return hm_rm_u_halfwave(X + i * ldx, Y + j * ldy, d1, sign_mode, lane);
-        });
-        if (t < HM_GATHER && mybase + t < total) out[mybase + t] = hm::dist_from_u(u, sqrt_c);
-    }
-}
-
-__global__ void hm_rows_minkowski_kernel(const float* __restrict__ x, const float* __restrict__ y, int64_t b, int64_t ld, int d1,
-                                         int sign_mode, float* __restrict__ out)
-{
-    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= b) return;
-    // minkowski_dot under the active convention = -u
-    out[t] = -hm_rm_u(x + t * ld, y + t * ld, d1, sign_mode);
-}
-
-__global__ __launch_bounds__(256) void hm_rows_distance_kernel(const float* __restrict__ x, const float* __restrict__ y, int64_t b, int64_t ld,
-                                                               int d1, float sqrt_c, int sign_mode, float* __restrict__ out)
-{
-    const int lane = threadIdx.x & 63, t = lane & 31;
-    const int64_t nhw = ((int64_t)gridDim.x * blockDim.x) >> 5;
-    const int64_t hw = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 5;
-    for (int64_t base = (hw & ~(int64_t)1) * HM_GATHER; base < b; base += nhw * HM_GATHER) {
-        const int64_t mybase = base + (hw & 1) * HM_GATHER;
-        const float u = hm_halfwave_gather(lane, [&](int k) {
-            const int64_t r = mybase + k < b ? mybase + k : b - 1;
-            return hm_rm_u_halfwave(x + r * ld, y + r * ld, d1, sign_mode, lane);
-        });
-        if (t < HM_GATHER && mybase + t < b) out[mybase + t] = hm::dist_from_u(u, sqrt_c);
-    }
-}
-
-__global__ void hm_rows_log_map_kernel(const float* __restrict__ x, const float* __restrict__ y, int64_t b, int64_t ld, int d1,
-                                       int sign_mode, float* __restrict__ out, int64_t ldo)
-{
-    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= b) return;
-    const float* xr = x + t * ld;
-    const float* yr = y + t * ld;
-    const float u = hm_rm_u(xr, yr, d1, sign_mode);
-    const float m = -u;
-    const float a = hm::clamp_min_one(u);
-    float coef = hm::acosh_c(a) / __builtin_sqrtf(a * a - 1.0f);
-    if (coef == coef && coef > 1.0e4f) coef = 1.0e4f;
-    for (int k = 0; k < d1; ++k) out[t * ldo + k] = coef * (yr[k] + m * xr[k]);
-}
-
-__global__ void hm_rows_exp_map_kernel(const float* __restrict__ x, const float* __restrict__ v, int64_t b, int64_t ld, int d1,
-                                       float* __restrict__ out, int64_t ldo)
-{
-    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= b) return;
-    const float* xr = x + t * ld;
-    const float* vr = v + t * ld;
-    float n2 = hm::torch_order_sum([&](int s) { return vr[1 + s] * vr[1 + s]; }, d1 - 1);
-    if (n2 == n2 && n2 < 1.0e-8f) n2 = 1.0e-8f;
-    const float nn = __builtin_sqrtf(n2);
-    const float ch = hm::cosh_c(nn), sh = hm::sinh_c(nn);
-    for (int k = 0; k < d1; ++k) out[t * ldo + k] = ch * xr[k] + sh * (vr[k] / nn);
-}
-
-__global__ void hm_rows_project_kernel(const float* __restrict__ x, int64_t b, int64_t ld, int d1, float c, float* __restrict__ out,
-                                       int64_t ldo)
-{
-    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= b) return;
-    const float* xr = x + t * ld;
-    float r2 = 0.0f;
-    for (int k = 1; k < d1; ++k) r2 = __builtin_fmaf(xr[k], xr[k], r2);
-    const float rr = __builtin_sqrtf(r2);
-    const float x0 = __builtin_sqrtf(1.0f + (c * rr) * rr);
-    for (int k = 1; k < d1; ++k) out[t * ldo + k] = xr[k];
-    out[t * ldo] = x0;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -572,9 +464,7 @@ extern "C" int hm_merge_append_batch_host(hm_engine* e, const int32_t* I_host, c
     HM_HIP(hipEventRecord(e->ev_batch, s));
     e->batch_in_flight = true;
     // (row-existence of the operands was checked above against first_row; hm_merge_append_batch checks the rest)
-    const int64_t n_keep = e->n;
     if (first_row > e->n) return hm_fail(e, HM_E_ARG, "hm_merge_append_batch_host: first_row beyond the live rows");
-    (void)n_keep;
     return hm_merge_append_batch(e, e->d_batch, e->d_batch + HM_BATCH_MAX, reinterpret_cast<const float*>(e->d_batch + 2 * HM_BATCH_MAX),
                                  count, c, X_dev, ld, first_row, independent, stream);
 }
@@ -612,75 +502,5 @@ extern "C" int hm_project_table(hm_engine* e, float* X_dev, int64_t ld, int64_t 
     e->armed = false;
     e->have_cut = false;
     e->topk_f32_thr = 0.0f; e->topk_exact_thr = 0.0f;
-    return HM_OK;
-}
-
-// ---- engine-independent entry points ----
-extern "C" int hm_batch_distance(const float* X_dev, int64_t n1, const float* Y_dev, int64_t n2, int64_t ld_x, int64_t ld_y, int d1,
-                                 float c, int sign_mode, float* out_dev, void* stream)
-{
-    if (n1 < 0 || n2 < 0 || d1 < 2 || ld_x < d1 || ld_y < d1 || !(c > 0.0f)) return hm_fail(nullptr, HM_E_ARG, "hm_batch_distance: bad arguments");
-    if (n1 == 0 || n2 == 0) return HM_OK;
-    if (!X_dev || !Y_dev || !out_dev) return hm_fail(nullptr, HM_E_ARG, "hm_batch_distance: NULL pointer");
-    const int64_t total = n1 * n2;
-    const unsigned blocks = (unsigned)std::min<int64_t>((total + 8 * HM_GATHER - 1) / (8 * HM_GATHER), 8192);
-    hipLaunchKernelGGL(hm_dense_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, X_dev, n1, Y_dev, n2, ld_x, ld_y, d1,
-                       sqrtf(c), sign_mode, out_dev);
-    HM_HIP0(hipGetLastError());
-    return HM_OK;
-}
-
-extern "C" int hm_rows_minkowski(const float* x_dev, const float* y_dev, int64_t b, int64_t ld, int d1, int sign_mode, float* out_dev,
-                                 void* stream)
-{
-    if (b < 0 || d1 < 2 || ld < d1) return hm_fail(nullptr, HM_E_ARG, "hm_rows_minkowski: bad arguments");
-    if (b == 0) return HM_OK;
-    hipLaunchKernelGGL(hm_rows_minkowski_kernel, dim3((unsigned)((b + 127) / 128)), dim3(128), 0, (hipStream_t)stream, x_dev, y_dev, b,
-                       ld, d1, sign_mode, out_dev);
-    HM_HIP0(hipGetLastError());
-    return HM_OK;
-}
-
-extern "C" int hm_rows_distance(const float* x_dev, const float* y_dev, int64_t b, int64_t ld, int d1, float c, int sign_mode,
-                                float* out_dev, void* stream)
-{
-    if (b < 0 || d1 < 2 || ld < d1 || !(c > 0.0f)) return hm_fail(nullptr, HM_E_ARG, "hm_rows_distance: bad arguments");
-    if (b == 0) return HM_OK;
-    hipLaunchKernelGGL(hm_rows_distance_kernel, dim3((unsigned)std::min<int64_t>((b + 8 * HM_GATHER - 1) / (8 * HM_GATHER), 8192)), dim3(256), 0, (hipStream_t)stream, x_dev, y_dev, b,
-                       ld, d1, sqrtf(c), sign_mode, out_dev);
-    HM_HIP0(hipGetLastError());
-    return HM_OK;
-}
-
-extern "C" int hm_rows_log_map(const float* x_dev, const float* y_dev, int64_t b, int64_t ld, int d1, int sign_mode, float* out_dev,
-                               int64_t ld_out, void* stream)
-{
-    if (b < 0 || d1 < 2 || ld < d1 || ld_out < d1) return hm_fail(nullptr, HM_E_ARG, "hm_rows_log_map: bad arguments");
-    if (b == 0) return HM_OK;
-    hipLaunchKernelGGL(hm_rows_log_map_kernel, dim3((unsigned)((b + 127) / 128)), dim3(128), 0, (hipStream_t)stream, x_dev, y_dev, b,
-                       ld, d1, sign_mode, out_dev, ld_out);
-    HM_HIP0(hipGetLastError());
-    return HM_OK;
-}
-
-extern "C" int hm_rows_exp_map(const float* x_dev, const float* v_dev, int64_t b, int64_t ld, int d1, float* out_dev, int64_t ld_out,
-                               void* stream)
-{
-    if (b < 0 || d1 < 2 || ld < d1 || ld_out < d1) return hm_fail(nullptr, HM_E_ARG, "hm_rows_exp_map: bad arguments");
-    if (b == 0) return HM_OK;
-    hipLaunchKernelGGL(hm_rows_exp_map_kernel, dim3((unsigned)((b + 127) / 128)), dim3(128), 0, (hipStream_t)stream, x_dev, v_dev, b,
-                       ld, d1, out_dev, ld_out);
-    HM_HIP0(hipGetLastError());
-    return HM_OK;
-}
-
-extern "C" int hm_rows_project(const float* x_dev, int64_t b, int64_t ld, int d1, float c, float* out_dev, int64_t ld_out,
-                               void* stream)
-{
-    if (b < 0 || d1 < 2 || ld < d1 || ld_out < d1) return hm_fail(nullptr, HM_E_ARG, "hm_rows_project: bad arguments");
-    if (b == 0) return HM_OK;
-    hipLaunchKernelGGL(hm_rows_project_kernel, dim3((unsigned)((b + 127) / 128)), dim3(128), 0, (hipStream_t)stream, x_dev, b, ld, d1,
-                       c, out_dev, ld_out);
-    HM_HIP0(hipGetLastError());
     return HM_OK;
 }

@@ -38,15 +38,11 @@ __device__ __forceinline__ float hm_wave_midpoint(int d, float w, float c, int s
     const float mref = t0 - S;
     const float u = sign_mode ? mref : -mref;
     const float m = -u;
-    const float a = hm::clamp_min_one(u);
-    float coef = hm::acosh_c(a) / __builtin_sqrtf(a * a - 1.0f);
-    if (coef == coef && coef > 1.0e4f) coef = 1.0e4f;
+    const float coef = hm::log_map_coef(u).coef;
     for (int k = lane; k <= d; k += 64) ms.sv[k] = (coef * (ms.sy[k] + m * ms.sx[k])) * w;     // w * log_map
     hm_wave_lds_sync();
     // exp_map (:73-93)
-    float n2 = hm_halfwave_sum(d, lane, [&](int e) { return ms.sv[1 + e] * ms.sv[1 + e]; });
-    if (n2 == n2 && n2 < 1.0e-8f) n2 = 1.0e-8f;
-    const float nn = __builtin_sqrtf(n2);
+    const float nn = hm::exp_map_norm(hm_halfwave_sum(d, lane, [&](int e) { return ms.sv[1 + e] * ms.sv[1 + e]; }));
     float ch, sh;
     hm::cosh_sinh_c(nn, ch, sh);                               // cosh_c / sinh_c with their common expm1 evaluated once
     for (int k = lane; k <= d; k += 64) ms.so[k] = ch * ms.sx[k] + sh * (ms.sv[k] / nn);
@@ -65,8 +61,7 @@ __device__ __forceinline__ float hm_wave_midpoint(int d, float w, float c, int s
 #pragma unroll
             for (int q = 0; q < 32; ++q) r2 = __builtin_fmaf(v[q], v[q], r2);
         }
-        const float rr = __builtin_sqrtf(r2);
-        const float x0 = __builtin_sqrtf(1.0f + (c * rr) * rr);
+        const float x0 = hm::project_x0(r2, c);
         hm_wave_lds_sync();
         if (lane == 0) ms.so[0] = x0;
         hm_wave_lds_sync();

@@ -22,11 +22,13 @@ def wants_grad(*tensors) -> bool:
 
 
 def _rows(t: torch.Tensor, shape) -> torch.Tensor:
+    """``t`` broadcast to ``shape`` as contiguous fp32 rows [b, shape[-1]].  No copy when it already is that; a broadcast,
+    strided or non-fp32 operand is materialised as a full [b, shape[-1]] fp32 copy (in the forward and again in the backward)."""
     return t.detach().expand(shape).reshape(-1, shape[-1]).contiguous().float()
 
 
 def _reduce(g: torch.Tensor, like: torch.Tensor, shape) -> torch.Tensor:
-    """Gradient of the broadcast operand [b, d1] back to ``like``'s shape and dtype."""
+    """Gradient of the broadcast operand back to ``like``'s shape and dtype."""
     return g.reshape(shape).sum_to_size(like.shape).to(like.dtype)
 
 

@@ -14,16 +14,11 @@ from torch.autograd.function import once_differentiable
 
 from .. import _lib
 from ..engine import _ptr, _require_cuda, _stream_of
+from ._autograd import _reduce, _rows
 
 MAX_D = 128
 
 _PAIR = ("mobius_add", "distance")                           # two row operands broadcast against each other
-
-
-def _rows(t: torch.Tensor, shape) -> torch.Tensor:
-    """``t`` broadcast to ``shape`` as contiguous fp32 rows [b, shape[-1]].  No copy when it already is that; a broadcast,
-    strided or non-fp32 operand is materialised as a full [b, shape[-1]] fp32 copy (in the forward and again in the backward)."""
-    return t.detach().expand(shape).reshape(-1, shape[-1]).contiguous().float()
 
 
 def _shapes(op: str, a: torch.Tensor, b):
@@ -82,11 +77,6 @@ def forward(op: str, a: torch.Tensor, b, c: float, standard: int = 0) -> torch.T
                 raise ValueError(op)
             _lib.check(st)
     return out.reshape(tuple(lead) + (width,))
-
-
-def _reduce(g: torch.Tensor, like: torch.Tensor, shape) -> torch.Tensor:
-    """Gradient of the broadcast operand back to ``like``'s shape and dtype."""
-    return g.reshape(shape).sum_to_size(like.shape).to(like.dtype)
 
 
 class _PoincareOp(torch.autograd.Function):
