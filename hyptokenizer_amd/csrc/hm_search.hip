@@ -986,7 +986,9 @@ static int hm_topk_impl(hm_engine* e, float c, float thr, int64_t k, int64_t row
         uint4* res = nullptr;
         int rc = hm_topk_core(e, c, thr, k, row_begin, row_end, false, want_count || k == 0, -1, &valid, &total, &res, s);
         if (rc) return rc;
-        *count = total;
+        // the uncounted form answers -1 once k candidates exist (include/hypmerge.h), also where a small table's search
+        // emitted every candidate and so knows their number
+        *count = (!want_count && k > 0 && total >= k) ? -1 : total;
         kk = (uint32_t)std::min<int64_t>(k, valid);
         if (kk == 0 || !res) { e->prev_valid = false; return HM_OK; }
         const uint32_t m = (uint32_t)std::min<uint64_t>(e->h->ctr64[2], e->ent_cap);

@@ -64,6 +64,31 @@ class OracleEngine:
             return None
         return float(d[0]), int(i[0]), int(j[0])
 
+    def argmin_into(self, c, thr, row_begin, row_end, rec):
+        """the record {found, bits(d), i, j} of ``MergeEngine.argmin_into`` (never found = 2: no emission buffer here)"""
+        hit = self.argmin(c, thr, row_begin, row_end)
+        self.calls["argmin"] -= 1
+        vals = [0, 0, -1, -1] if hit is None else [1, int(bits([hit[0]])[0]), hit[1], hit[2]]
+        rec[:4] = torch.tensor(vals, dtype=torch.int32)
+
+    def topk_refresh_begin(self, c, thr, k):
+        """always of the incremental kind here: the refresh is answered by a plain uncounted top-k of the table as it is"""
+        if getattr(self, "_refresh", None) is not None:
+            raise RuntimeError("a top-k refresh is pending on this engine: call topk_refresh_end() first")
+        self._refresh = (c, thr, int(k))
+        return True
+
+    def topk_refresh_end(self):
+        if getattr(self, "_refresh", None) is None:
+            raise RuntimeError("no refresh pending")
+        (c, thr, k), self._refresh = self._refresh, None
+        d, i, j, _ = self.topk(c, thr, k, count=False)
+        self.calls["topk"] -= 1
+        return d, i, j
+
+    def set_prefilter(self, prefilter):
+        """results never depend on the prefilter form: nothing to do"""
+
     def candidates(self, c, thr, row_begin=0, row_end=-1, cap=1 << 24):
         self.calls["candidates"] += 1
         r0, r1 = self._range(row_begin, row_end)
