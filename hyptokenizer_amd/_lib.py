@@ -55,6 +55,8 @@ EXPORTED_SYMBOLS = (
     "hm_graph_create", "hm_graph_destroy", "hm_graph_set_csr", "hm_graph_components", "hm_graph_pair_lengths",
     "hm_graph_distance_rows", "hm_graph_last_stats", "hm_tokstats",
     "hm_rsgd_step", "hm_radam_step",
+    "hm_edge_loss_fwd", "hm_edge_loss_bwd", "hm_debug_edge_loss_form", "hm_negsample_create", "hm_negsample_destroy", "hm_negsample_check_csr",
+    "hm_negsample_set_csr", "hm_negsample_sample",
 )
 
 
@@ -195,6 +197,14 @@ def load() -> C.CDLL:
     L.hm_rows_poincare_to_lorentz_bwd.argtypes = [vp, vp, i64, i64, i64, C.c_int, f32, C.c_int, vp, i64, vp]
     L.hm_rsgd_step.argtypes = [vp, i64, vp, i64, vp, i64, vp, i64, i64, C.c_int, f32, f32, f32, C.c_int, vp]
     L.hm_radam_step.argtypes = [vp, i64, vp, i64, vp, i64, vp, vp, i64, i64, C.c_int, f32, f32, f32, f32, f32, f32, vp]
+    L.hm_edge_loss_fwd.argtypes = [vp, i64, i64, C.c_int, vp, i64, i64, f32, vp, vp, vp]
+    L.hm_edge_loss_bwd.argtypes = [vp, i64, i64, C.c_int, vp, i64, i64, f32, vp, vp, vp, vp, vp]
+    L.hm_debug_edge_loss_form.argtypes = [C.c_int]
+    L.hm_negsample_create.argtypes = [C.POINTER(vp), C.c_int]
+    L.hm_negsample_destroy.argtypes = [vp]
+    L.hm_negsample_check_csr.argtypes = [vp, vp, i64]
+    L.hm_negsample_set_csr.argtypes = [vp, vp, vp, i64, vp]
+    L.hm_negsample_sample.argtypes = [vp, vp, i64, i64, C.c_uint64, i64, C.c_int, vp, vp]
     L.hm_graph_create.argtypes = [C.POINTER(vp), C.c_int]
     L.hm_graph_destroy.argtypes = [vp]
     L.hm_graph_set_csr.argtypes = [vp, vp, vp, i64, vp]

@@ -1,0 +1,380 @@
+// hm_edgeloss.hip -- the graph-embedding objective of Nickel & Kiela (2017, 2018) on a Lorentz table, forward and backward
+// (DESIGN.md 5.17).  Engine-independent like hm_riemann.hip, whose sparse path consumes what the backward kernel writes.
+//
+// index [B, 2 + K] int64: column 0 the anchor u, column 1 the positive, columns 2.. the negatives.  Partner k = 0 is the
+// positive, partner k >= 1 the negative of column 1 + k; P = 1 + K partners.  A negative outside [0, V) is a skipped slot, a
+// sample whose anchor or positive lies outside [0, V) is skipped whole; neither is ever dereferenced.
+//   u_k    = x_u0 x_k0 - sum_s x_us x_ks          canonical u of hm_grad_device.h ("lorentz" sign), ATen's summation order;
+//                                                 a partner that IS the anchor (same index) has u_k = 1 by definition
+//   d_k    = acosh(max(u_k, 1)) / sqrt(c)         hm::dist_from_u: the bits of hm_rows_distance
+//   loss_b = d_0 + log sum_{k live} exp(-d_k)     shifted by max_k(-d_k) = -min_k d_k
+//   a_k    = ([k = 0] - p_k) / (sqrt(c) sqrt(u_k^2 - 1)), p = softmax(-d) over the live slots; a_k = 0 where u_k <= 1
+//   grad   anchor: sum_k a_k (x_k0, -x_ks);  partner k: a_k (x_u0, -x_us)            (Euclidean, -J x = (x0, -xs))
+//
+// Layout: the lane groups of hm_rowgroup.h, 16 (d <= 64) or 32 lanes per row, scalar form (the spatial part starts one column
+// into the row), the time column a per-row scalar beside the slots as in hm_riemann.hip.  A group keeps the anchor row in
+// registers and walks partners with EL_FLIGHT partner rows loaded before the first is used.  Two forms (hm_debug_edge_loss_form):
+//   form 0  one GROUP per sample: the group walks all P partners (4 or 2 samples per wave);
+//   form 1  one WAVE per sample: its S = 4 or 2 groups take the partners k = g, g + S, g + 2 S, ... and combine d_min, the sum
+//           of exponentials and the anchor's gradient by butterflies across the wave -- S times the waves, P / S the walk.
+// Below, "position" i of group g is partner k = g + S i (form 0: S = 1, g = 0).
+//   forward   pass 1: u_k by the whole group (el_canon_sum: hm_halfwave_sum's chains laid over the group's slots), parked in
+//             lane k % G, which evaluates d_k once and stores u_k to the weights w [B, P];
+//             pass 2: every lane re-reads the u_k IT stored, sums exp(-(d_k - d_min)), one butterfly;
+//             pass 3: the same lanes turn their u_k into a_k in place.
+//   backward  re-gathers the partner rows, carries the anchor's sum in registers across the partner loop, and writes every
+//             value row [B, 2 + K, d1] and every COO index exactly once: no atomics, no workspace but w.
+#include "hm_rowgroup.h"
+#include "hm_grad_device.h"
+
+#pragma clang fp contract(off)
+
+#define EL_THREADS 64                                         // one wave per block: 4 or 2 samples, so that small batches spread
+#define EL_FLIGHT 4                                           // partner rows in flight per group
+
+struct ElArgs {
+    const float* x;
+    const int64_t* index;
+    float* w;                                                 // [B, P]: u_k inside the forward kernel, a_k once it has finished
+    float* loss;                                              // forward: [B]
+    const float* gl;                                          // backward: upstream gradient of loss [B]
+    float* val;                                               // backward: [B * (2 + K), d1]
+    int64_t* coo;                                             // backward: [B * (2 + K)]
+    int64_t ld, B, V;
+    int K, d, lsh, split;
+    float sqrt_c;
+};
+
+__device__ __forceinline__ bool el_in(int64_t i, int64_t V) { return i >= 0 && i < V; }
+__device__ __forceinline__ float el_pick(const float (&p)[4], int j) { return j == 0 ? p[0] : j == 1 ? p[1] : j == 2 ? p[2] : p[3]; }
+
+// Sum of the row's d products pr (element e in slot e >> lsh of lane e & (G - 1); slots past d hold 0) in the order of
+// hm::torch_order_sum, bit for bit, on every lane of the group.  ATen's 32 chains: chain t takes elements t, t + 32, ... below
+// 32 ilp; a group of 32 lanes holds chain t in lane t (slots 0 .. ilp - 1), a group of 16 holds chains t and t + 16 in lane t
+// (even and odd slots).  Then hm_halfwave_sum's combine: leftover vectors of 8 into chains 0..7, chains l, l + 8, l + 16,
+// l + 24 added in that order, the scalar tail summed from zero, the eight sums in order.  Every branch is uniform.
+__device__ __forceinline__ float el_canon_sum(const RgMap& q, int d, const float (&pr)[4])
+{
+    const int G = 1 << q.lsh, t = q.sub;
+    if (d < 8) {                                              // scalar form: element e is slot 0 of lane e (G = 16)
+        float ps[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+        const int full = (d >> 2) * 4;
+#pragma unroll
+        for (int e = 0; e < 7; ++e) {
+            const float v = __shfl(pr[0], e, 16);
+            if (e < full) ps[e & 3] = ps[e & 3] + v;
+            else if (e < d) ps[0] = ps[0] + v;
+        }
+        ps[0] = ps[0] + ps[1];
+        ps[0] = ps[0] + ps[2];
+        ps[0] = ps[0] + ps[3];
+        return ps[0];
+    }
+    const int vec = d >> 3, ilp = vec >> 2, nleft = vec - ilp * 4, ntail = d - vec * 8;
+    float pa = 0.0f, pb = 0.0f;
+    float c1, c2, c3;
+    if (q.lsh == 5) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+            if (j < ilp) pa = pa + pr[j];
+    } else {
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+            if (i < ilp) { pa = pa + pr[2 * i]; pb = pb + pr[2 * i + 1]; }
+    }
+#pragma unroll
+    for (int v = 0; v < 3; ++v) {
+        if (v < nleft) {
+            const int e0 = 32 * ilp + 8 * v;                  // first element of the leftover vector: 8 elements of one slot
+            const float got = __shfl(el_pick(pr, e0 >> q.lsh), (e0 & (G - 1)) + (t & 7), G);
+            if (t < 8) pa = pa + got;
+        }
+    }
+    if (q.lsh == 5) {
+        c1 = __shfl(pa, (t & 7) + 8, 32);
+        c2 = __shfl(pa, (t & 7) + 16, 32);
+        c3 = __shfl(pa, (t & 7) + 24, 32);
+    } else {
+        c1 = __shfl(pa, (t & 7) + 8, 16);
+        c2 = __shfl(pb, (t & 7), 16);
+        c3 = __shfl(pb, (t & 7) + 8, 16);
+    }
+    const float r = ((pa + c1) + c2) + c3;                    // meaningful on lanes t < 8
+    float acc = 0.0f;
+#pragma unroll
+    for (int v = 0; v < 7; ++v) {
+        if (v < ntail) {
+            const int e = vec * 8 + v;
+            acc = acc + __shfl(el_pick(pr, e >> q.lsh), e & (G - 1), G);
+        }
+    }
+#pragma unroll
+    for (int l = 0; l < 8; ++l) acc = acc + __shfl(r, l, G);
+    return acc;
+}
+
+// butterflies over the lanes that share a sample: `width` = the group (form 0) or the wave (form 1)
+__device__ __forceinline__ float el_min(int width, float a)
+{
+    for (int off = width >> 1; off > 0; off >>= 1) a = fminf(a, __shfl_xor(a, off, 64));
+    return a;
+}
+__device__ __forceinline__ float el_sum(int width, float a)
+{
+    for (int off = width >> 1; off > 0; off >>= 1) a = a + __shfl_xor(a, off, 64);
+    return a;
+}
+
+// lane -> (sample, group of the sample, lane of the group); a block is one wave
+__device__ __forceinline__ RgMap el_map(const ElArgs& a, int& gid, int& S)
+{
+    if (!a.split) {
+        gid = 0;
+        S = 1;
+        return rg_map(a.lsh, 0, a.B);
+    }
+    RgMap m;
+    m.lsh = a.lsh;
+    m.vec = 0;
+    m.sub = (int)(threadIdx.x & ((1u << a.lsh) - 1u));
+    m.row = (int64_t)blockIdx.x;
+    m.live = m.row < a.B;
+    gid = (int)(threadIdx.x >> a.lsh);
+    S = EL_THREADS >> a.lsh;
+    return m;
+}
+
+// the sample of this group: its anchor and whether it is served
+struct ElSample {
+    const int64_t* ix;
+    int64_t iu;
+    bool ok;
+};
+
+__device__ __forceinline__ ElSample el_sample(const ElArgs& a, const RgMap& q)
+{
+    ElSample s;
+    s.ix = a.index + q.row * (int64_t)(2 + a.K);
+    s.iu = q.live ? s.ix[0] : -1;
+    const int64_t iv = q.live ? s.ix[1] : -1;
+    s.ok = q.live && el_in(s.iu, a.V) && el_in(iv, a.V);
+    return s;
+}
+
+__global__ __launch_bounds__(EL_THREADS) void hm_el_fwd_kernel(const ElArgs a)
+{
+    int gid, S;
+    const RgMap q = el_map(a, gid, S);
+    const ElSample s = el_sample(a, q);
+    const int G = 1 << a.lsh, d = a.d, P = 1 + a.K;
+    const int Pp = (P + S - 1) / S, width = G * S;               // positions per group; lanes that share the sample
+    RgMap qa = q;
+    qa.live = s.ok;
+    const float* xr = a.x + (s.ok ? s.iu : 0) * a.ld;
+    float xs[4];
+    const float x0 = s.ok ? xr[0] : 1.0f;
+    rg_load(xr + 1, d, qa, xs);
+    float* wr = a.w + q.row * (int64_t)P;
+
+    // pass 1: u_k, parked in lane k % G; d_min and d_0
+    float dmin = INFINITY, d0 = 0.0f;
+    for (int c0 = 0; c0 < Pp; c0 += G) {
+        float myu = 1.0f;
+        bool mylive = false;
+        for (int kk = 0; kk < G && c0 + kk < Pp; kk += EL_FLIGHT) {
+            int64_t idx[EL_FLIGHT];
+            bool lv[EL_FLIGHT];
+            float y0[EL_FLIGHT], ys[EL_FLIGHT][4];
+#pragma unroll
+            for (int r = 0; r < EL_FLIGHT; ++r) {
+                const int k = gid + S * (c0 + kk + r);
+                idx[r] = (s.ok && k < P) ? s.ix[1 + k] : -1;
+                lv[r] = el_in(idx[r], a.V);
+            }
+#pragma unroll
+            for (int r = 0; r < EL_FLIGHT; ++r) {
+                RgMap qk = q;
+                qk.live = lv[r];
+                const float* yr = a.x + (lv[r] ? idx[r] : 0) * a.ld;
+                y0[r] = lv[r] ? yr[0] : 1.0f;
+                rg_load(yr + 1, d, qk, ys[r]);
+            }
+#pragma unroll
+            for (int r = 0; r < EL_FLIGHT; ++r) {
+                float pr[4];
+#pragma unroll
+                for (int j = 0; j < 4; ++j) pr[j] = xs[j] * ys[r][j];
+                const float S = el_canon_sum(q, d, pr);
+                const float t0 = x0 * y0[r];
+                const float u = (idx[r] == s.iu) ? 1.0f : t0 - S;
+                if (q.sub == kk + r) { myu = u; mylive = lv[r]; }
+            }
+        }
+        const int k = gid + S * (c0 + q.sub);
+        const float dk = mylive ? hm::dist_from_u(myu, a.sqrt_c) : INFINITY;
+        if (q.live && k < P) wr[k] = mylive ? myu : 1.0f;
+        if (c0 == 0) d0 = __shfl(dk, 0, width);                  // partner 0: position 0 of group 0
+        dmin = fminf(dmin, el_min(width, dk));
+    }
+
+    // pass 2: the shifted sum, every lane over the slots it stored
+    float sum = 0.0f;
+    for (int c0 = 0; c0 < Pp; c0 += G) {
+        const int k = gid + S * (c0 + q.sub);
+        if (s.ok && k < P && el_in(s.ix[1 + k], a.V)) sum = sum + expf(dmin - hm::dist_from_u(wr[k], a.sqrt_c));
+    }
+    sum = el_sum(width, sum);
+    const float lse = logf(sum) - dmin;
+    if (q.live && q.sub == 0 && gid == 0) a.loss[q.row] = s.ok ? d0 + lse : 0.0f;
+
+    // pass 3: u_k -> a_k in place
+    for (int c0 = 0; c0 < Pp; c0 += G) {
+        const int k = gid + S * (c0 + q.sub);
+        if (!q.live || k >= P) continue;
+        float ak = 0.0f;
+        if (s.ok && el_in(s.ix[1 + k], a.V)) {
+            const float u = wr[k];
+            if (u > 1.0f) {
+                const float p = expf(dmin - hm::dist_from_u(u, a.sqrt_c)) / sum;
+                ak = ((k == 0 ? 1.0f : 0.0f) - p) / (a.sqrt_c * __builtin_sqrtf(u * u - 1.0f));
+            }
+        }
+        wr[k] = ak;
+    }
+}
+
+// one value row: time by the group's first lane, the spatial part by rg_store
+__device__ __forceinline__ void el_store_row(float* __restrict__ r, int d, const RgMap& q, float v0, const float (&vs)[4])
+{
+    if (q.live && q.sub == 0) r[0] = v0;
+    rg_store(r + 1, d, q, vs);
+}
+
+__global__ __launch_bounds__(EL_THREADS) void hm_el_bwd_kernel(const ElArgs a)
+{
+    int gid, S;
+    const RgMap q = el_map(a, gid, S);
+    const ElSample s = el_sample(a, q);
+    const int d = a.d, d1 = a.d + 1, P = 1 + a.K;
+    const int Pp = (P + S - 1) / S;
+    RgMap qa = q;
+    qa.live = s.ok;
+    const float* xr = a.x + (s.ok ? s.iu : 0) * a.ld;
+    float xs[4], acc[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+    const float x0 = s.ok ? xr[0] : 0.0f;
+    rg_load(xr + 1, d, qa, xs);
+    const float g = q.live ? a.gl[q.row] : 0.0f;
+    const float* wr = a.w + q.row * (int64_t)P;
+    const int64_t slot0 = q.row * (int64_t)(2 + a.K);
+    const int64_t fill = s.ok ? s.iu : 0;                     // COO index of a skipped slot: its value row is zero
+    float acc0 = 0.0f;
+    for (int i0 = 0; i0 < Pp; i0 += EL_FLIGHT) {
+        int64_t idx[EL_FLIGHT];
+        bool lv[EL_FLIGHT];
+        float ak[EL_FLIGHT], y0[EL_FLIGHT], ys[EL_FLIGHT][4];
+#pragma unroll
+        for (int r = 0; r < EL_FLIGHT; ++r) {
+            const int k = gid + S * (i0 + r);
+            idx[r] = (s.ok && k < P) ? s.ix[1 + k] : -1;
+            lv[r] = el_in(idx[r], a.V);
+            ak[r] = lv[r] ? wr[k] : 0.0f;
+        }
+#pragma unroll
+        for (int r = 0; r < EL_FLIGHT; ++r) {
+            RgMap qk = q;
+            qk.live = lv[r];
+            const float* yr = a.x + (lv[r] ? idx[r] : 0) * a.ld;
+            y0[r] = lv[r] ? yr[0] : 0.0f;
+            rg_load(yr + 1, d, qk, ys[r]);
+        }
+#pragma unroll
+        for (int r = 0; r < EL_FLIGHT; ++r) {
+            const int k = gid + S * (i0 + r);
+            if (k >= P) continue;
+            acc0 = acc0 + ak[r] * y0[r];
+            float vs[4];
+            const float ga = g * ak[r];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                acc[j] = acc[j] - ak[r] * ys[r][j];
+                vs[j] = lv[r] ? -(ga * xs[j]) : 0.0f;
+            }
+            el_store_row(a.val + (slot0 + 1 + k) * d1, d, q, lv[r] ? ga * x0 : 0.0f, vs);
+            if (q.live && q.sub == 0) a.coo[slot0 + 1 + k] = lv[r] ? idx[r] : fill;
+        }
+    }
+    // form 1: the groups' partial sums of the anchor's gradient, lane by lane across the wave; group 0 stores the row
+    for (int off = 1 << a.lsh; off < (S << a.lsh); off <<= 1) {
+        acc0 = acc0 + __shfl_xor(acc0, off, 64);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) acc[j] = acc[j] + __shfl_xor(acc[j], off, 64);
+    }
+    float vs[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) vs[j] = s.ok ? g * acc[j] : 0.0f;
+    RgMap q0 = q;
+    q0.live = q.live && gid == 0;
+    el_store_row(a.val + slot0 * d1, d, q0, s.ok ? g * acc0 : 0.0f, vs);
+    if (q0.live && q.sub == 0) a.coo[slot0] = fill;
+}
+
+// ------------------------------------------------------------------------------------------------
+// C ABI
+// ------------------------------------------------------------------------------------------------
+static int g_el_form = 1;
+
+static int el_args(const char* who, const float* x_dev, int64_t ld, int64_t V, int d1, const int64_t* index_dev, int64_t B, int64_t K,
+                   float c, ElArgs& a)
+{
+    if (d1 < 2 || d1 > HM_RG_MAX_D + 1 || ld < d1 || V < 0 || V > ((int64_t)1 << 40) || B < 0 || B >= ((int64_t)1 << 31) || K < 0 ||
+        K > ((int64_t)1 << 20) || (B + 1) * (K + 2) > ((int64_t)1 << 40) || !(c > 0.0f) || !(c < INFINITY))
+        return hm_fail(nullptr, HM_E_ARG, std::string(who) + ": bad arguments");
+    if (!x_dev || !index_dev) return hm_fail(nullptr, HM_E_ARG, std::string(who) + ": NULL pointer");
+    a = ElArgs{};
+    a.x = x_dev; a.index = index_dev;
+    a.ld = ld; a.B = B; a.V = V;
+    a.K = (int)K; a.d = d1 - 1; a.lsh = rg_lsh(a.d); a.split = g_el_form;
+    a.sqrt_c = sqrtf(c);
+    return HM_OK;
+}
+
+static inline dim3 el_grid(const ElArgs& a)
+{
+    return dim3((unsigned)(a.split ? a.B : ((a.B << a.lsh) + EL_THREADS - 1) / EL_THREADS));
+}
+
+// Test / tuning hook: 0 = one lane group per sample, 1 = one wave per sample (the default), for the calls that follow.  The
+// two forms differ in the order of the sums over the partners, not in any u_k or d_k.
+extern "C" int hm_debug_edge_loss_form(int form)
+{
+    if (form != 0 && form != 1) return hm_fail(nullptr, HM_E_ARG, "hm_debug_edge_loss_form: form must be 0 or 1");
+    g_el_form = form;
+    return HM_OK;
+}
+
+extern "C" int hm_edge_loss_fwd(const float* x_dev, int64_t ld, int64_t table_rows, int d1, const int64_t* index_dev, int64_t n, int64_t k,
+                                float c, float* loss_dev, float* weights_dev, void* stream)
+{
+    ElArgs a;
+    if (int rc = el_args("hm_edge_loss_fwd", x_dev, ld, table_rows, d1, index_dev, n, k, c, a)) return rc;
+    if (!loss_dev || !weights_dev) return hm_fail(nullptr, HM_E_ARG, "hm_edge_loss_fwd: NULL pointer");
+    if (n == 0) return HM_OK;
+    a.loss = loss_dev; a.w = weights_dev;
+    hipLaunchKernelGGL(hm_el_fwd_kernel, el_grid(a), dim3(EL_THREADS), 0, (hipStream_t)stream, a);
+    HM_HIP0(hipGetLastError());
+    return HM_OK;
+}
+
+extern "C" int hm_edge_loss_bwd(const float* x_dev, int64_t ld, int64_t table_rows, int d1, const int64_t* index_dev, int64_t n, int64_t k,
+                                float c, const float* weights_dev, const float* grad_loss_dev, float* values_dev, int64_t* coo_dev,
+                                void* stream)
+{
+    ElArgs a;
+    if (int rc = el_args("hm_edge_loss_bwd", x_dev, ld, table_rows, d1, index_dev, n, k, c, a)) return rc;
+    if (!weights_dev || !grad_loss_dev || !values_dev || !coo_dev) return hm_fail(nullptr, HM_E_ARG, "hm_edge_loss_bwd: NULL pointer");
+    if (n == 0) return HM_OK;
+    a.w = const_cast<float*>(weights_dev); a.gl = grad_loss_dev; a.val = values_dev; a.coo = coo_dev;
+    hipLaunchKernelGGL(hm_el_bwd_kernel, el_grid(a), dim3(EL_THREADS), 0, (hipStream_t)stream, a);
+    HM_HIP0(hipGetLastError());
+    return HM_OK;
+}

@@ -1,0 +1,113 @@
+#!/usr/bin/env python
+"""Embed a graph in hyperbolic space: ``fit_graph_embedding`` (edge-softmax loss, negative sampler and Riemannian
+optimiser, all on the HIP device) from the command line.
+
+``--graph-path`` is the pickle ``scripts/eval_hierarchy.py`` reads (``load_wordnet_graph``), or a text file with one edge per
+line, two node names separated by a tab; node indices are then the order of first appearance.  Writes ``embeddings.pt`` (fp32
+``[V, dim + 1]``), ``nodes.json`` (node names in row order) and ``train_log.json`` (hyper-parameters and the mean loss of every
+epoch) to ``--output-dir``; with ``--eval-pairs N > 0`` also ``distortion_stats.json`` from ``compute_distortion`` over N
+sampled pairs.  The reference has no counterpart: it never trains its embeddings.
+"""
+from __future__ import annotations
+
+import json
+import logging
+import os
+from typing import Dict, List, Tuple
+
+import torch
+import typer
+
+from hyptokenizer_amd.embedding.graph_embedding import GraphEmbeddingResult, fit_graph_embedding
+from hyptokenizer_amd.scripts.eval_hierarchy import compute_distortion, load_wordnet_graph, set_seeds
+
+logging.basicConfig(level=logging.INFO, format="%(asctime)s - %(name)s - %(levelname)s - %(message)s")
+logger = logging.getLogger(__name__)
+
+
+class EdgeListGraph:
+    """The two methods ``GraphPaths`` and ``NegativeSampler`` ask of a graph, over a list of named edges."""
+
+    def __init__(self, edges: List[Tuple[str, str]]):
+        self._edges = list(edges)
+        self._nodes: Dict[str, None] = {}
+        for a, b in self._edges:
+            self._nodes.setdefault(a)
+            self._nodes.setdefault(b)
+
+    def nodes(self):
+        return list(self._nodes)
+
+    def edges(self):
+        return list(self._edges)
+
+
+def load_edge_list(path: str) -> EdgeListGraph:
+    """One edge per line, two node names separated by a tab; empty lines and lines starting with ``#`` are skipped."""
+    edges = []
+    with open(path, "r", encoding="utf-8") as f:
+        for no, line in enumerate(f, 1):
+            line = line.rstrip("\n")
+            if not line.strip() or line.startswith("#"):
+                continue
+            parts = line.split("\t")
+            if len(parts) != 2 or not parts[0] or not parts[1]:
+                raise ValueError(f"{path}:{no}: expected two tab-separated node names")
+            edges.append((parts[0], parts[1]))
+    return EdgeListGraph(edges)
+
+
+def load_graph(graph_path: str):
+    if graph_path.endswith((".tsv", ".txt")):
+        return load_edge_list(graph_path)
+    return load_wordnet_graph(graph_path)
+
+
+def train_graph_embeddings(graph_path: str, output_dir: str, dim: int = 10, epochs: int = 50, batch_size: int = 1024,
+                           num_negatives: int = 50, lr: float = 0.3, burn_in_epochs: int = 10, burn_in_factor: float = 0.1,
+                           optimizer: str = "rsgd", init_scale: float = 1e-3, seed: int = 0, curvature: float = 1.0,
+                           eval_pairs: int = 0, log_every: int = 1) -> GraphEmbeddingResult:
+    graph = load_graph(graph_path)
+    params = dict(dim=dim, epochs=epochs, batch_size=batch_size, num_negatives=num_negatives, lr=lr, burn_in_epochs=burn_in_epochs,
+                  burn_in_factor=burn_in_factor, optimizer=optimizer, init_scale=init_scale, seed=seed, c=curvature)
+    result = fit_graph_embedding(graph, log_every=log_every, **params)
+    os.makedirs(output_dir, exist_ok=True)
+    torch.save(result.table.cpu(), os.path.join(output_dir, "embeddings.pt"))
+    with open(os.path.join(output_dir, "nodes.json"), "w") as f:
+        json.dump([str(n) for n in result.node_names], f)
+    with open(os.path.join(output_dir, "train_log.json"), "w") as f:
+        json.dump(dict(params, graph_path=graph_path, nodes=len(result.node_names), loss_history=result.loss_history), f, indent=4)
+    logger.info(f"Saved embeddings of {len(result.node_names)} nodes to {output_dir}")
+    if eval_pairs > 0:
+        set_seeds(seed)
+        _, stats = compute_distortion(graph, result.table, result.node_mapping, num_pairs=eval_pairs, curvature=curvature,
+                                      device=result.table.device, sign_convention="lorentz")
+        with open(os.path.join(output_dir, "distortion_stats.json"), "w") as f:
+            json.dump(stats, f, indent=4)
+    return result
+
+
+def main(
+    graph_path: str = "data/processed/wordnet_graph.gpk",
+    output_dir: str = "results/graph_embedding",
+    dim: int = 10,
+    epochs: int = 50,
+    batch_size: int = 1024,
+    num_negatives: int = 50,
+    lr: float = 0.3,
+    burn_in_epochs: int = 10,
+    burn_in_factor: float = 0.1,
+    optimizer: str = "rsgd",
+    init_scale: float = 1e-3,
+    seed: int = 0,
+    curvature: float = 1.0,
+    eval_pairs: int = 0,
+) -> None:
+    """Train hyperbolic embeddings of a graph."""
+    train_graph_embeddings(graph_path=graph_path, output_dir=output_dir, dim=dim, epochs=epochs, batch_size=batch_size,
+                           num_negatives=num_negatives, lr=lr, burn_in_epochs=burn_in_epochs, burn_in_factor=burn_in_factor,
+                           optimizer=optimizer, init_scale=init_scale, seed=seed, curvature=curvature, eval_pairs=eval_pairs)
+
+
+if __name__ == "__main__":
+    typer.run(main)

@@ -640,6 +640,47 @@ int hm_radam_step(float* x_dev, int64_t ld_x, const float* g_dev, int64_t ld_g, 
                   const int64_t* rows_dev, int64_t n, int64_t table_rows, int d1, float lr, float beta1, float beta2, float eps,
                   float bc1, float bc2, void* stream);
 
+/* ---- graph embedding: the edge-softmax loss on a Lorentz table and its negative sampler ---------------
+ * x [table_rows, ld] fp32 points of the hyperboloid (d1 = d + 1 columns, 2 <= d1 <= 129), index int64 [n, 2 + k] on the
+ * device: column 0 the anchor, column 1 the positive, columns 2.. the negatives.  A negative outside [0, table_rows) is a
+ * skipped slot (-1 is the documented mask), a sample whose anchor or positive lies outside is skipped whole (loss 0);
+ * neither is dereferenced.  With u_j = x_u0 x_j0 - sum_s x_us x_js in the canonical order (exactly 1 for a partner that is
+ * the anchor itself) and d_j = acosh(max(u_j, 1)) / sqrt(c) -- the bits of hm_rows_distance under HM_SIGN_LORENTZ --
+ *   loss[b] = d_0 + log sum_{j live} exp(-d_j)                        (positive inside the sum, shifted by its maximum)
+ *   a_j     = ([j = 0] - softmax(-d)_j) / (sqrt(c) sqrt(u_j^2 - 1)), and 0 where u_j <= 1 (NOT the infinite derivative of
+ *             hm_rows_distance_bwd at coincident rows).
+ * hm_edge_loss_fwd writes loss_dev [n] and weights_dev [n, 1 + k] = a_j (0 for a skipped slot), the only state between
+ * the two calls.  hm_edge_loss_bwd takes grad_loss_dev [n] and writes the Euclidean gradient in COO form, slot order:
+ * values_dev [n * (2 + k), d1], row (b, 0) = g_b sum_j a_j (x_j0, -x_js), row (b, 1 + j) = g_b a_j (x_u0, -x_us), and
+ * coo_dev int64 [n * (2 + k)] = index with a skipped slot replaced by the anchor (by 0 when the sample is skipped), its
+ * value row zero.  Every row is written once, no atomics: two calls on the same inputs give the same bits.
+ * Engine-independent; errors through hm_last_error(NULL); asynchronous on `stream`.  HM_E_ARG before the device is touched
+ * for a NULL pointer, d1 outside 2..129, ld < d1, negative table_rows / n / k, c not positive and finite.  n == 0: HM_OK,
+ * no launch.  Replaces: nothing the reference runs (it has no trainer). */
+int hm_edge_loss_fwd(const float* x_dev, int64_t ld, int64_t table_rows, int d1, const int64_t* index_dev, int64_t n, int64_t k,
+                     float c, float* loss_dev, float* weights_dev, void* stream);
+int hm_edge_loss_bwd(const float* x_dev, int64_t ld, int64_t table_rows, int d1, const int64_t* index_dev, int64_t n, int64_t k,
+                     float c, const float* weights_dev, const float* grad_loss_dev, float* values_dev, int64_t* coo_dev, void* stream);
+/* Test / tuning hook: the work decomposition of the two calls above from now on -- 0: one lane group per sample, 1: one wave
+ * per sample (the default).  Losses and gradients agree to rounding (another order of the sums over the
+ * partners); d_0 and every u_k are the same bits. */
+int hm_debug_edge_loss_form(int form);
+
+/* Negative sampler.  The graph is a symmetric CSR as for hm_graph_set_csr (HOST arrays, 1 <= n < 2^31) whose rows are
+ * additionally sorted and free of repeats (HM_E_ARG otherwise; hm_negsample_check_csr is that check alone and touches no
+ * device).  hm_negsample_sample: pairs_dev int64 [n_pairs, 2] -> out_dev int64 [n_pairs, 2 + k], columns 0 and 1 copied,
+ * slot j of sample b the first candidate of attempts t = 0 .. max_tries - 1 that is neither the anchor nor adjacent to it,
+ * candidate = (uint64(r) * n) >> 32 with r the first output word of Philox4x32-10 under key (seed low, seed high) and
+ * counter (b, j, t, step); -1 when every attempt was rejected or the anchor lies outside [0, n).  0 <= step < 2^32,
+ * 1 <= max_tries <= 65536.  Asynchronous on `stream`; hm_negsample_set_csr synchronises it. */
+typedef struct hm_negsample hm_negsample;
+int hm_negsample_create(hm_negsample** out, int device);
+int hm_negsample_destroy(hm_negsample* g);
+int hm_negsample_check_csr(const int64_t* row_ptr, const int32_t* col, int64_t n);
+int hm_negsample_set_csr(hm_negsample* g, const int64_t* row_ptr, const int32_t* col, int64_t n, void* stream);
+int hm_negsample_sample(hm_negsample* g, const int64_t* pairs_dev, int64_t n_pairs, int64_t k, uint64_t seed, int64_t step,
+                        int max_tries, int64_t* out_dev, void* stream);
+
 /* Test hook: pretend the previous refresh ended on this emission cut (bits of u'); the next whole-table top-k
  * search starts from it as given and has to notice by itself when it is too tight. */
 int hm_debug_force_cut(hm_engine* e, uint32_t cut_bits, int64_t k, float c);
