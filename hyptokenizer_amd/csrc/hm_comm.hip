@@ -216,7 +216,7 @@ extern "C" int hm_global_argmin(hm_engine* e, float c, float thr, float* d, int3
             if (q.found == 2u) overflow = true;
             if (q.found == 1u && (q.dbits < b0 || (q.dbits == b0 && (q.i < b1 || (q.i == b1 && q.j < b2))))) { b0 = q.dbits; b1 = q.i; b2 = q.j; }
         }
-        if (overflow && pass == 0) { e->armed = false; continue; }
+        if (overflow && pass == 0) { e->st.disarm(); continue; }
         if (b1 != 0xffffffffu) {
             union { uint32_t u; float f; } cv; cv.u = b0;
             *found = 1; *d = cv.f; *i = (int32_t)b1; *j = (int32_t)b2;
@@ -256,7 +256,7 @@ extern "C" int hm_global_topk(hm_engine* e, float c, float thr, int64_t k, float
     hipStream_t s = (hipStream_t)stream;
     HM_HIP(hipSetDevice(e->device));
     *n_out = 0; *count = 0;
-    e->armed = false;
+    e->st.disarm();
     int64_t r0 = 0, r1 = 0;
     hm_partition_rows(e->n, e->world, e->rank, &r0, &r1);
     // this rank's ordered list stays on the device (e->sorted); its exact candidate count comes back with it
@@ -273,7 +273,7 @@ extern "C" int hm_global_topk(hm_engine* e, float c, float thr, int64_t k, float
             if (rc) return rc;
         }
     }
-    e->have_cut = false; e->prev_valid = false;              // (range searches do not feed the whole-table refresh state)
+    e->st.drop_list();                                       // (range searches do not feed the whole-table refresh state)
     uint4* mine = e->d_gather;                               // [k + 1] packed list of this rank, then [world][k + 1] gathered
     uint4* all = e->d_gather + (k + 1);
     hipLaunchKernelGGL(hm_gather_pack_kernel, dim3(64), dim3(256), 0, s, e->sorted, kk, (uint32_t)k, (unsigned long long)total, mine);

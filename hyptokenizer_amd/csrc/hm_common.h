@@ -1,6 +1,7 @@
 // hm_common.h -- internal declarations shared by the translation units of libhypmerge.so.
 //
 //   hm_engine.hip   engine lifetime, table upload, statistics            (host)
+//   hm_state.h      the search state carried from call to call and its named transitions (host)
 //   hm_scan.hip     the pair-scan kernel (MFMA prefilter) and its launch  (hot kernel)
 //   hm_search.hip   exact re-evaluation / selection kernels and the search entry points of the ABI
 //   hm_rows.hip     the engine's row work: image construction, merge / midpoint, one-row-vs-all and gathered distances
@@ -45,6 +46,7 @@
 
 #include "../../include/hypmerge.h"
 #include "hm_device_math.h"
+#include "hm_state.h"
 
 #pragma clang fp contract(off)
 
@@ -232,15 +234,12 @@ struct hm_engine {
     LoopState* d_loop = nullptr;
     int32_t* d_len = nullptr;              // token lengths (device-resident loops), max_rows entries
     bool have_len = false;
-    float topk_f32_thr = 0.0f;
     bool force_exact = false;                   // knob exact_search
-    float topk_exact_thr = 0.0f;                // > 0: whole searches at thresholds >= this one go straight to the exact path (hm_exact.hip)
     uint32_t* d_rowcnt = nullptr;               // hm_exact.hip: per-row counts (allocated on first use)
     unsigned long long* d_xhist = nullptr;      // hm_exact.hip: 64-bit digit histogram, HM_EXACT_BINS (allocated on first use)
     LoopState* h_loop = nullptr;                // pinned host image of a LoopState: the incremental loop's initial state goes up, and its final state comes back, in ONE copy each
-    bool force_f32 = false;
-    bool armed = false;
-    int64_t armed_rb = 0, armed_re = 0;
+    bool force_f32 = false;                     // set for the length of one retry (HmScopedSet)
+    SearchState st;                             // arming, cut prediction, previous list, route memories, pending refresh (hm_state.h)
     ArgminSeed* d_seed = nullptr;
     ArgminPart* d_parts = nullptr;
     uint32_t* d_hist = nullptr;
@@ -256,11 +255,6 @@ struct hm_engine {
     hipStream_t aux = nullptr;
     hipEvent_t ev_scan[2] = {nullptr, nullptr}, ev_tail[2] = {nullptr, nullptr}, ev_join = nullptr;
     unsigned long long* d_rowkey = nullptr;     // [0], [1]: the pipelined loop's two sets; [2]: hm_row_argmin
-    // cut prediction for top-k: valid while rows are only appended
-    bool have_cut = false;
-    uint32_t last_cut_bits = 0;
-    int64_t last_cut_k = 0;
-    float last_cut_c = 0.f;
     // the ordered list of the last whole-table top-k search (device copy): while rows are only appended, the next one is
     // the k smallest of (that list) + (pairs with a new row)
     uint4* d_prev = nullptr;
@@ -269,16 +263,7 @@ struct hm_engine {
     int32_t* d_batch = nullptr;
     hipEvent_t ev_batch = nullptr;
     bool batch_in_flight = false;
-    bool prev_valid = false;
     bool incremental_topk = true;         // HM_TUNE_INCR_TOPK=0: every refresh scans the whole triangle
-    int64_t prev_k = 0, prev_n = 0;
-    float prev_thr = 0.f;
-    bool debug_cut = false;               // hm_debug_force_cut: the next top-k starts from last_cut_bits as given
-    // hm_topk_refresh_begin .. _end
-    bool refresh_pending = false;
-    int64_t refresh_k = 0;
-    float refresh_c = 0.f, refresh_thr = 0.f;
-    void* refresh_stream = nullptr;
     // row-sharded device-resident loop (hm_shard_loop_begin .. _end): searches skip themselves once the loop has stopped
     bool shard_loop = false;
     int64_t shard_n0 = 0;
@@ -311,6 +296,24 @@ struct hm_engine {
 };
 
 int hm_fail(hm_engine* e, int code, const std::string& msg);
+// ---- hm_engine.hip ----
+// rows from first_changed_row on were written: when that is an existing row, the state that rests on the old rows is void
+// (SearchState::row_changed) and the argmin seed is zeroed on the stream
+int hm_rows_changed(hm_engine* e, int64_t first_changed_row, hipStream_t s);
+// statistics of one search (hm_last_scan_stats): begin takes in a pending device-side timing and zeroes them; add reads the
+// engine's event pair (ev0, ev1) behind a synchronised scan of `pairs` pairs
+void hm_scan_stats_begin(hm_engine* e);
+void hm_scan_stats_add(hm_engine* e, int64_t pairs, int64_t emitted);
+// an override that lasts for one scope (force_f32 and pipeline around a retry): no return path leaves it switched on
+template <class T>
+struct HmScopedSet {
+    T& ref;
+    const T old;
+    HmScopedSet(T& r, T v) : ref(r), old(r) { ref = v; }
+    ~HmScopedSet() { ref = old; }
+    HmScopedSet(const HmScopedSet&) = delete;
+    HmScopedSet& operator=(const HmScopedSet&) = delete;
+};
 // hm_graph.hip: default knobs of the graph component.  HM_OK: taken; HM_E_ARG: bad value; 1: not one of its knobs
 int hm_graph_default_knob(const char* name, double value, int clear);
 bool hm_graph_owns_knob(const char* name);

@@ -68,7 +68,7 @@ static int hm_apply_knob(hm_engine* e, const char* name, double v)
         if (v != 0.0 && (e->KC & 1)) { e->KC += 1; e->RB16 = 16 * hm_row16_chunks(e->KC); }
     }
     else return HM_E_ARG;
-    e->armed = false;
+    e->st.disarm();
     return HM_OK;
 }
 
@@ -248,9 +248,7 @@ extern "C" int hm_set_prefilter(hm_engine* e, int prefilter)
     if (!e) return hm_fail(nullptr, HM_E_ARG, "hm_set_prefilter: engine is NULL");
     if (prefilter < HM_PREFILTER_AUTO || prefilter > HM_PREFILTER_BF16) return hm_fail(e, HM_E_ARG, "hm_set_prefilter: bad value");
     e->precision = prefilter;
-    e->armed = false;                    // the seed's margin belongs to the form that wrote it: start the next search afresh
-    e->have_cut = false;
-    e->topk_f32_thr = 0.0f; e->topk_exact_thr = 0.0f;
+    e->st.table_replaced();              // the armed counters' margin belongs to the form that wrote them: the next search starts afresh (d_seed stays)
     return HM_OK;
 }
 
@@ -259,7 +257,7 @@ extern "C" int64_t hm_rows(const hm_engine* e) { return e ? e->n : -1; }
 extern "C" int hm_set_table(hm_engine* e, const float* X_dev, int64_t ld, int64_t n_rows, void* stream)
 {
     if (!e) return hm_fail(nullptr, HM_E_ARG, "hm_set_table: engine is NULL");
-    e->armed = false;
+    e->st.disarm();
     if (!X_dev || ld < e->d1 || n_rows < 0 || n_rows > e->max_rows)
         return hm_fail(e, HM_E_ARG, "hm_set_table: bad table pointer / ld / n_rows");
     hipStream_t s = (hipStream_t)stream;
@@ -272,8 +270,7 @@ extern "C" int hm_set_table(hm_engine* e, const float* X_dev, int64_t ld, int64_
     int rc = hm_build_rows(e, X_dev, ld, 0, n_rows, s);
     if (rc) return rc;
     e->n = n_rows;
-    e->have_cut = false;
-    e->topk_f32_thr = 0.0f; e->topk_exact_thr = 0.0f;
+    e->st.table_replaced();
     HM_HIP(hipMemsetAsync(e->d_seed, 0, sizeof(ArgminSeed), s));      // new table: no seed
     return HM_OK;
 }
@@ -281,17 +278,24 @@ extern "C" int hm_set_table(hm_engine* e, const float* X_dev, int64_t ld, int64_
 extern "C" int hm_update_rows(hm_engine* e, const float* X_dev, int64_t ld, int64_t row_begin, int64_t row_end, void* stream)
 {
     if (!e) return hm_fail(nullptr, HM_E_ARG, "hm_update_rows: engine is NULL");
-    e->armed = false;
+    e->st.disarm();
     if (!X_dev || ld < e->d1 || row_begin < 0 || row_end < row_begin || row_end > e->max_rows)
         return hm_fail(e, HM_E_ARG, "hm_update_rows: bad arguments");
     HM_HIP(hipSetDevice(e->device));
     int rc = hm_build_rows(e, X_dev, ld, row_begin, row_end, (hipStream_t)stream);
     if (rc) return rc;
-    if (row_begin < e->n) {                          // an existing row changed: cut prediction and argmin seed void
-        e->have_cut = false;
-        HM_HIP(hipMemsetAsync(e->d_seed, 0, sizeof(ArgminSeed), (hipStream_t)stream));
-    }
+    rc = hm_rows_changed(e, row_begin, (hipStream_t)stream);
+    if (rc) return rc;
     if (row_end > e->n) e->n = row_end;
+    return HM_OK;
+}
+
+int hm_rows_changed(hm_engine* e, int64_t first_changed_row, hipStream_t s)
+{
+    if (first_changed_row < e->n) {          // an existing row changed: cut prediction, argmin seed and arming are void
+        e->st.row_changed();
+        HM_HIP(hipMemsetAsync(e->d_seed, 0, sizeof(ArgminSeed), s));
+    }
     return HM_OK;
 }
 
@@ -343,6 +347,23 @@ void hm_flush_pending_timing(hm_engine* e)
     e->pending_timing = false;
 }
 
+void hm_scan_stats_begin(hm_engine* e)
+{
+    hm_flush_pending_timing(e);
+    e->last_scan_ms = 0.f; e->last_pairs = 0; e->last_emitted = 0; e->last_passes = 0;
+}
+
+void hm_scan_stats_add(hm_engine* e, int64_t pairs, int64_t emitted)
+{
+    float ms = 0.f;
+    (void)hipEventElapsedTime(&ms, e->ev0, e->ev1);
+    e->last_scan_ms += ms;
+    e->last_passes += 1;
+    e->last_pairs = pairs;
+    e->tot_scan_ms += ms; e->tot_pairs += pairs; e->tot_launches += 1;
+    e->last_emitted = emitted;
+}
+
 // the per-scan event pairs of the last complete device batch (hm_debug_time_loops), read on demand
 void hm_read_loop_events(hm_engine* e)
 {
@@ -387,11 +408,7 @@ extern "C" int hm_scan_totals(hm_engine* e, double* scan_ms, int64_t* pairs, int
 extern "C" int hm_debug_force_cut(hm_engine* e, uint32_t cut_bits, int64_t k, float c)
 {
     if (!e) return HM_E_ARG;
-    e->have_cut = true;
-    e->last_cut_bits = cut_bits;
-    e->last_cut_k = k;
-    e->last_cut_c = c;
-    e->debug_cut = true;
+    e->st.force_cut(cut_bits, k, c);
     return HM_OK;
 }
 

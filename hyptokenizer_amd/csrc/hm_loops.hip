@@ -39,10 +39,8 @@ extern "C" int hm_truncate(hm_engine* e, int64_t n_rows, void* stream)
     if (e->n > n_rows) {
         HM_HIP(hipMemsetAsync(e->img + n_rows * e->RS, 0, sizeof(float) * (size_t)(e->n - n_rows) * e->RS, s));
         HM_HIP(hipMemsetAsync(e->img16 + n_rows * e->RB16, 0, (size_t)(e->n - n_rows) * e->RB16, s));
-        e->armed = false;
-        e->have_cut = false;
-        HM_HIP(hipMemsetAsync(e->d_seed, 0, sizeof(ArgminSeed), s));
     }
+    if (const int rc = hm_rows_changed(e, n_rows, s)) return rc;      // rows were removed: as if they had changed
     e->n = n_rows;
     return HM_OK;
 }
@@ -253,8 +251,7 @@ extern "C" int hm_std_merge_steps(hm_engine* e, float c, float thr, float* X_dev
     const int64_t n0 = e->n;
     const float sqrt_c = sqrtf(c);
     HM_HIP(hipMemsetAsync(e->d_loop, 0, sizeof(LoopState), s));
-    bool armed = e->armed && e->armed_rb == 0 && e->armed_re == -1;
-    e->armed = false;
+    bool armed = e->st.take_arm(0, -1);
     int64_t timed_pairs = 0;
     const bool time_all = e->time_loops && !e->loop_evs.empty();
     if (time_all) hm_read_loop_events(e);         // the events are about to be reused
@@ -302,13 +299,11 @@ extern "C" int hm_std_merge_steps(hm_engine* e, float c, float thr, float* X_dev
     e->n = n0 + *done;
     if (piped && *done < steps && e->h->ctr[7] == 5u) {
         // a scan's order guard tripped (never seen outside the test hook): the steps from there on, strictly sequentially
-        e->armed = false;
+        e->st.disarm();
         e->pipe_fault_at = -1;
-        const bool keep = e->pipeline;
-        e->pipeline = false;
+        const HmScopedSet<bool> sequential(e->pipeline, false);
         int64_t done2 = 0;
         const int rc2 = hm_std_merge_steps(e, c, thr, X_dev, ld, steps - *done, rec_out + 4 * *done, &done2, stream);
-        e->pipeline = keep;
         if (rc2) return rc2;
         *done += done2;
         return HM_OK;
@@ -317,12 +312,13 @@ extern "C" int hm_std_merge_steps(hm_engine* e, float c, float thr, float* X_dev
         // a step left more survivors than the pipelined tail's small grid takes (typically the first search on a new table,
         // before a seed bounds the emissions): that ONE step through the sequential chain and its full-size tail, the rest
         // pipelined again
-        e->armed = false;
-        const bool keep = e->pipeline;
-        e->pipeline = false;
+        e->st.disarm();
         int64_t done2 = 0;
-        int rc2 = hm_std_merge_steps(e, c, thr, X_dev, ld, 1, rec_out + 4 * *done, &done2, stream);
-        e->pipeline = keep;
+        int rc2;
+        {
+            const HmScopedSet<bool> sequential(e->pipeline, false);
+            rc2 = hm_std_merge_steps(e, c, thr, X_dev, ld, 1, rec_out + 4 * *done, &done2, stream);
+        }
         if (rc2) return rc2;
         *done += done2;
         if (done2 == 1 && *done < steps) {
@@ -335,8 +331,8 @@ extern "C" int hm_std_merge_steps(hm_engine* e, float c, float thr, float* X_dev
         return HM_OK;
     }
     e->pipe_fault_at = -1;
-    e->armed = (*done == steps) && !piped;         // (the pipelined batch leaves its two sets armed for ITS next steps only)
-    e->armed_rb = 0; e->armed_re = -1;
+    if (*done == steps && !piped) e->st.arm(0, -1); // (the pipelined batch leaves its two sets armed for ITS next steps only)
+    else e->st.disarm();
     if (time_all) {
         e->last_batch_ms = e->last_batch_scan_ms = 0.f;
         e->last_batch_steps = 0;
@@ -464,7 +460,7 @@ extern "C" int hm_incr_merge_steps(hm_engine* e, float c, float thr, float* X_de
     if (e->n + steps > e->max_rows) return hm_fail(e, HM_E_CAPACITY, "hm_incr_merge_steps: the table cannot take that many rows");
     hipStream_t s = (hipStream_t)stream;
     HM_HIP(hipSetDevice(e->device));
-    e->armed = false;
+    e->st.disarm();
     const int64_t n0 = e->n;
     // initial state in one copy: zeros, best[0] = the caller's nearest pair, row keys of this batch's steps = "none"
     if (!e->h_loop) HM_HIP(hipHostMalloc(&e->h_loop, sizeof(LoopState), hipHostMallocDefault));
@@ -629,6 +625,6 @@ extern "C" int hm_shard_loop_end(hm_engine* e, int64_t steps, uint32_t* rec_out,
         hm_unpack_recs(e->h->loop_recs, steps, rec_out, done);
     }
     e->n = e->shard_n0 + *done;
-    if (*done < steps) e->armed = false;          // a search that skipped itself armed nothing
+    if (*done < steps) e->st.disarm();            // a search that skipped itself armed nothing
     return HM_OK;
 }

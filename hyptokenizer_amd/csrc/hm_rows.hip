@@ -396,15 +396,6 @@ extern "C" int hm_midpoint_batch(hm_engine* e, const int32_t* I_dev, const int32
     return HM_OK;
 }
 
-static void hm_rows_changed(hm_engine* e, int64_t first_changed_row, hipStream_t s)
-{
-    if (first_changed_row < e->n) {          // an existing row changed: cut prediction, argmin seed and arming are void
-        e->armed = false;
-        e->have_cut = false;
-        (void)hipMemsetAsync(e->d_seed, 0, sizeof(ArgminSeed), s);
-    }
-}
-
 extern "C" int hm_merge_append(hm_engine* e, int32_t i, int32_t j, float w, float c, float* X_dev, int64_t ld, int64_t new_row,
                                void* stream)
 {
@@ -415,7 +406,7 @@ extern "C" int hm_merge_append(hm_engine* e, int32_t i, int32_t j, float w, floa
     hipLaunchKernelGGL(hm_merge_append_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, e->img, e->RS, e->d, i, j, w, c,
                        e->sign_mode, X_dev, ld, new_row, e->d_rmax2, e->img16, e->KC);
     HM_HIP(hipGetLastError());
-    hm_rows_changed(e, new_row, (hipStream_t)stream);
+    if (const int rc = hm_rows_changed(e, new_row, (hipStream_t)stream)) return rc;
     if (new_row + 1 > e->n) e->n = new_row + 1;
     return HM_OK;
 }
@@ -436,7 +427,7 @@ extern "C" int hm_merge_append_batch(hm_engine* e, const int32_t* I_dev, const i
         hipLaunchKernelGGL(hm_merge_batch_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, e->img, e->RS, e->d, I_dev, J_dev, W_dev,
                            (int)count, c, e->sign_mode, X_dev, ld, first_row, e->d_rmax2, e->img16, e->KC);
     HM_HIP(hipGetLastError());
-    hm_rows_changed(e, first_row, (hipStream_t)stream);
+    if (const int rc = hm_rows_changed(e, first_row, (hipStream_t)stream)) return rc;
     if (first_row + count > e->n) e->n = first_row + count;
     return HM_OK;
 }
@@ -499,8 +490,6 @@ extern "C" int hm_project_table(hm_engine* e, float* X_dev, int64_t ld, int64_t 
                        e->img, e->RS, e->img16, e->KC, e->n, fresh, e->d_rmax2, e->d_seed);
     HM_HIP(hipGetLastError());
     e->d_rmax2 = fresh;
-    e->armed = false;
-    e->have_cut = false;
-    e->topk_f32_thr = 0.0f; e->topk_exact_thr = 0.0f;
+    e->st.table_replaced();
     return HM_OK;
 }

@@ -589,20 +589,21 @@ int hm_topk_core(hm_engine* e, float c, float thr, int64_t k, int64_t row_begin,
 {
     const bool had_bf16 = hm_use_bf16(e);
     int rc = HM_E_CAPACITY;
-    const bool exact_known = !list_all && (e->force_exact || (e->topk_exact_thr > 0.0f && thr >= e->topk_exact_thr));      // (remembered per table, like the fp32 fallback)
-    if (!exact_known && !(had_bf16 && e->topk_f32_thr > 0.0f && thr >= e->topk_f32_thr))
+    const bool exact_known = !list_all && (e->force_exact || e->st.straight_to_exact(thr));      // (remembered per table, like the fp32 fallback)
+    if (!exact_known && !(had_bf16 && e->st.straight_to_f32(thr)))
         rc = hm_topk_core_form(e, c, thr, k, row_begin, row_end, list_all, want_count, n_limit, n_valid_emitted, count, result_dev, s);
     if (!exact_known && rc == HM_E_CAPACITY && had_bf16 && !e->force_f32) {
-        e->force_f32 = true;
-        rc = hm_topk_core_form(e, c, thr, k, row_begin, row_end, list_all, want_count, n_limit, n_valid_emitted, count, result_dev, s);
-        e->force_f32 = false;
-        if (rc == HM_OK && !(e->topk_f32_thr > 0.0f && e->topk_f32_thr <= thr)) e->topk_f32_thr = thr;
+        {
+            const HmScopedSet<bool> f32(e->force_f32, true);
+            rc = hm_topk_core_form(e, c, thr, k, row_begin, row_end, list_all, want_count, n_limit, n_valid_emitted, count, result_dev, s);
+        }
+        if (rc == HM_OK) e->st.remember_f32(thr);
     }
     if (rc == HM_E_CAPACITY && !list_all) {
         // No emission cut fits the buffer in either prefilter form (a table whose distances sit within a few hundred ulps of
         // u = 1): every pair evaluated exactly, selection by counting (hm_exact.hip).  Slow, and always an answer.
         rc = hm_topk_exact(e, c, thr, k, row_begin, row_end, n_limit, n_valid_emitted, count, result_dev, s);
-        if (rc == HM_OK && !(e->topk_exact_thr > 0.0f && e->topk_exact_thr <= thr)) e->topk_exact_thr = thr;
+        if (rc == HM_OK) e->st.remember_exact(thr);
     }
     return rc;
 }
@@ -615,8 +616,7 @@ static int hm_topk_core_form(hm_engine* e, float c, float thr, int64_t k, int64_
     *n_valid_emitted = 0;
     *count = 0;
     *result_dev = nullptr;
-    hm_flush_pending_timing(e);
-    e->last_scan_ms = 0.f; e->last_pairs = 0; e->last_emitted = 0; e->last_passes = 0;
+    hm_scan_stats_begin(e);
     const Bounds b = hm_bounds(thr, c);
     ScanArgs a; dim3 grid;
     if (b.none || e->n < 2 || !hm_prepare_scan(e, b, row_begin, row_end, a, grid, n_limit)) return HM_OK;
@@ -630,9 +630,9 @@ static int hm_topk_core_form(hm_engine* e, float c, float thr, int64_t k, int64_
         cut_bits = 0x3f800000u;          // a pure count: nothing has to be emitted but the undecided shell around the threshold
         tie_imax = -1;
     } else if (!list_all) {
-        if (whole && e->have_cut && e->last_cut_k >= k && e->last_cut_c == c && e->last_cut_bits > 0x3f800000u) {
-            cut_bits = e->debug_cut ? e->last_cut_bits : e->last_cut_bits + hm_tie_slack(e->last_cut_bits);
-            e->debug_cut = false;
+        const SearchState::Cut& cut = e->st.cut();
+        if (whole && cut.have && cut.k >= k && cut.c == c && cut.bits > 0x3f800000u) {
+            cut_bits = e->st.consume_debug_cut() ? cut.bits : cut.bits + hm_tie_slack(cut.bits);
         } else {
             int rc = hm_estimate_cut(e, a, grid, 4 * k + 4096, &cut_bits, &tie_imax, s);
             if (rc) return rc;
@@ -656,13 +656,7 @@ static int hm_topk_core_form(hm_engine* e, float c, float thr, int64_t k, int64_
         HM_HIP(hipMemcpyAsync(e->h->ctr, e->d_ctr, sizeof(uint32_t) * 8, hipMemcpyDeviceToHost, s));
         HM_HIP(hipMemcpyAsync(e->h->ctr64, e->d_ctr64, sizeof(unsigned long long) * 4, hipMemcpyDeviceToHost, s));
         HM_HIP(hipStreamSynchronize(s));
-        float ms = 0.f;
-        (void)hipEventElapsedTime(&ms, e->ev0, e->ev1);
-        e->last_scan_ms += ms;
-        e->last_passes += 1;
-        e->last_pairs = hm_pairs_in_range(a.n, a.row_begin, a.row_end);
-        e->tot_scan_ms += ms; e->tot_pairs += e->last_pairs; e->tot_launches += 1;
-        e->last_emitted = (int64_t)e->h->ctr64[2];
+        hm_scan_stats_add(e, hm_pairs_in_range(a.n, a.row_begin, a.row_end), (int64_t)e->h->ctr64[2]);
         if (e->h->ctr[4] != 0)
             return hm_fail(e, HM_E_STATE, "pair scan: prefilter margin violated (an entry classified as surely below the "
                                           "threshold is not); table holds non-finite rows other than all-NaN rows?");
@@ -740,8 +734,7 @@ extern "C" int hm_pairwise_argmin_dev(hm_engine* e, float c, float thr, int64_t 
     const Bounds b = hm_bounds(thr, c);
     ScanArgs a; dim3 grid;
     const int64_t req_rb = std::max<int64_t>(row_begin, 0), req_re = (row_end < 0 || row_end >= e->n) ? -1 : row_end;
-    const bool skip_init = e->armed && e->armed_rb == req_rb && e->armed_re == req_re;
-    e->armed = false;
+    const bool skip_init = e->st.take_arm(req_rb, req_re);
     if (b.none || e->n < 2 || !hm_prepare_scan(e, b, row_begin, row_end, a, grid)) {
         HM_HIP(hipMemsetAsync(rec_dev, 0, sizeof(ArgminRec), s));        // found = 0
         return HM_OK;
@@ -768,7 +761,7 @@ extern "C" int hm_pairwise_argmin_dev(hm_engine* e, float c, float thr, int64_t 
     // Armed optimistically: the host does not see this record.  Should the search have overflowed (found = 2, the
     // kernel then arms nothing), the next search of this range starts on the stale counters, reports found = 2 as
     // well, and its caller takes the bounded host path -- slower, never wrong.
-    e->armed = true; e->armed_rb = req_rb; e->armed_re = req_re;
+    e->st.arm(req_rb, req_re);
     if (timed) {
         e->pending_timing = true;
         e->pending_pairs = hm_pairs_in_range(e->n, a.row_begin, a.row_end);
@@ -785,16 +778,14 @@ extern "C" int hm_pairwise_argmin(hm_engine* e, float c, float thr, int64_t row_
     hipStream_t s = (hipStream_t)stream;
     HM_HIP(hipSetDevice(e->device));
     *found = 0; *d = 0.f; *i = -1; *j = -1;
-    hm_flush_pending_timing(e);
-    e->last_scan_ms = 0.f; e->last_pairs = 0; e->last_emitted = 0; e->last_passes = 0;
+    hm_scan_stats_begin(e);
     const Bounds b = hm_bounds(thr, c);
     ScanArgs a; dim3 grid;
     // the range as asked, "to the end" normalised (the table grows between searches): what "same range" means
     const int64_t req_rb = std::max<int64_t>(row_begin, 0), req_re = (row_end < 0 || row_end >= e->n) ? -1 : row_end;
-    const bool skip_init = e->armed && e->armed_rb == req_rb && e->armed_re == req_re;
-    e->armed = false;
+    const bool skip_init = e->st.take_arm(req_rb, req_re);
     if (b.none || e->n < 2 || !hm_prepare_scan(e, b, row_begin, row_end, a, grid)) return HM_OK;
-    if (e->force_exact || (e->topk_exact_thr > 0.0f && thr >= e->topk_exact_thr)) {
+    if (e->force_exact || e->st.straight_to_exact(thr)) {
         // this table's searches are known to end in the prefilter-free path (hm_exact.hip): no scan attempts first
         float d1 = 0.f; int32_t i1 = -1, j1 = -1; int64_t n1 = 0, cnt1 = 0;
         const int rc2 = hm_pairwise_topk_nocount(e, c, thr, 1, row_begin, row_end, &d1, &i1, &j1, &n1, &cnt1, stream);
@@ -823,21 +814,13 @@ extern "C" int hm_pairwise_argmin(hm_engine* e, float c, float thr, int64_t row_
         HM_HIP(hipStreamSynchronize(s));
         e->h->rec = e->h->rec2[0];
         const uint64_t emitted = (uint64_t)e->h->rec2[1].found | ((uint64_t)e->h->rec2[1].dbits << 32);
-        float ms = 0.f;
-        (void)hipEventElapsedTime(&ms, e->ev0, e->ev1);
-        e->last_scan_ms += ms;
-        e->last_passes += 1;
-        e->last_pairs = hm_pairs_in_range(e->n, a.row_begin, a.row_end);
-        e->tot_scan_ms += ms; e->tot_pairs += e->last_pairs; e->tot_launches += 1;
-        e->last_emitted = (int64_t)emitted;
+        hm_scan_stats_add(e, hm_pairs_in_range(e->n, a.row_begin, a.row_end), (int64_t)emitted);
         if (emitted <= e->ent_cap) break;
         // overflow: the running key is the exact minimum over all published waves; rerun bounded by it
         if (pass == 1) {
             if (a.bf16 && !e->force_f32) {      // the bf16 margin's shell around the bound is too populated: fp32 prefilter
-                e->force_f32 = true;
-                const int rc2 = hm_pairwise_argmin(e, c, thr, row_begin, row_end, d, i, j, found, stream);
-                e->force_f32 = false;
-                return rc2;
+                const HmScopedSet<bool> f32(e->force_f32, true);
+                return hm_pairwise_argmin(e, c, thr, row_begin, row_end, d, i, j, found, stream);
             }
             // Still too many pairs inside the running key's slack band (a very dense table: the band is 1024 ulps of
             // u, which near u = 1 spans every distance below ~0.016): take the first entry of an exact top-1 search,
@@ -853,7 +836,7 @@ extern "C" int hm_pairwise_argmin(hm_engine* e, float c, float thr, int64_t row_
         union { uint32_t u; float f; } cv; cv.u = e->h->rec.dbits;
         *found = 1; *d = cv.f; *i = (int32_t)e->h->rec.i; *j = (int32_t)e->h->rec.j;
     }
-    if (e->h->rec.found != 2u) { e->armed = true; e->armed_rb = req_rb; e->armed_re = req_re; }
+    if (e->h->rec.found != 2u) e->st.arm(req_rb, req_re);
     return HM_OK;
 }
 
@@ -865,8 +848,7 @@ extern "C" int hm_pairwise_argmin(hm_engine* e, float c, float thr, int64_t row_
 // when the incremental refresh applies (checked by its callers)
 static bool hm_topk_incremental_ok(const hm_engine* e, float c, float thr, int64_t k)
 {
-    return k > 0 && e->incremental_topk && e->have_cut && e->prev_valid && e->prev_k == k && e->last_cut_c == c && thr >= e->prev_thr &&
-           e->n >= e->prev_n && e->n - e->prev_n <= 8192 && e->last_cut_bits > 0x3f800000u && !e->debug_cut;
+    return e->incremental_topk && e->st.incremental_ok(e->n, c, thr, k);
 }
 
 // entries the device-side sort takes: the pairs of a few hundred new rows under the previous list's cut are often several
@@ -876,18 +858,17 @@ static uint32_t hm_topk_incremental_limit(const hm_engine* e) { return std::min<
 // everything of the incremental refresh up to the read-back, enqueued; no host wait
 static int hm_topk_incremental_enqueue(hm_engine* e, float c, float thr, int64_t k, hipStream_t s)
 {
-    hm_flush_pending_timing(e);
-    e->last_scan_ms = 0.f; e->last_pairs = 0; e->last_emitted = 0; e->last_passes = 0;
+    hm_scan_stats_begin(e);
     const Bounds b = hm_bounds(thr, c);
     const uint32_t lim = hm_topk_incremental_limit(e);
     if ((uint64_t)k + 1 > lim) return HM_E_CAPACITY;
     HM_HIP(hipMemsetAsync(e->d_ctr, 0, sizeof(uint32_t) * 8, s));
     HM_HIP(hipMemsetAsync(e->d_ctr64, 0, sizeof(unsigned long long) * 4, s));
-    if (e->n > e->prev_n) {
+    if (e->n > e->st.prev().n) {
         ScanArgs a; dim3 grid;
-        if (!hm_prepare_scan(e, b, 0, -1, a, grid, -1, e->prev_n)) return hm_fail(e, HM_E_STATE, "incremental refresh: empty scan");
+        if (!hm_prepare_scan(e, b, 0, -1, a, grid, -1, e->st.prev().n)) return hm_fail(e, HM_E_STATE, "incremental refresh: empty scan");
         a.count_sure = 0;
-        a.cut_bits = e->last_cut_bits + hm_tie_slack(e->last_cut_bits);
+        a.cut_bits = e->st.cut().bits + hm_tie_slack(e->st.cut().bits);
         a.tie_imax = 0x7fffffff;
         HM_HIP(hm_launch_scan(e, HM_MODE_TOPK, a, grid, s));
         hipLaunchKernelGGL(hm_post_distance_kernel, dim3(256), dim3(256), 0, s, e->ent, e->d_ctr64, e->ent_cap, e->img, e->RS, e->d,
@@ -945,27 +926,15 @@ static void hm_topk_publish(hm_engine* e, uint32_t kk, int64_t k, float c, float
     *n_out = kk;
     // remember the largest u' of the selection: while rows are only appended, the k-th smallest key can
     // only move down, so this cut (+ tie slack) is a guaranteed superset for the next refresh
-    if (keep) {
-        e->have_cut = true;
-        e->last_cut_bits = mx;
-        e->last_cut_k = k;
-        e->last_cut_c = c;
-        e->prev_valid = true;
-        e->prev_k = k;
-        e->prev_n = e->n;
-        e->prev_thr = thr;
-    } else {
-        e->have_cut = false;
-        e->prev_valid = false;
-    }
+    e->st.publish(keep, mx, k, c, e->n, thr);
 }
 
 // common body of hm_pairwise_topk / hm_pairwise_topk_nocount
 static int hm_topk_impl(hm_engine* e, float c, float thr, int64_t k, int64_t row_begin, int64_t row_end, bool want_count,
                         float* d_out, int32_t* i_out, int32_t* j_out, int64_t* n_out, int64_t* count, void* stream)
 {
-    if (e) e->armed = false;
     if (!e) return hm_fail(nullptr, HM_E_ARG, "hm_pairwise_topk: engine is NULL");
+    e->st.disarm();                                // (before the argument checks: a refused top-k disarms too)
     if (!n_out || !count || k < 0 || (k > 0 && (!d_out || !i_out || !j_out)))
         return hm_fail(e, HM_E_ARG, "hm_pairwise_topk: bad output pointers / k");
     if (!(c > 0.0f)) return hm_fail(e, HM_E_ARG, "hm_pairwise_topk: curvature must be > 0");
@@ -990,7 +959,7 @@ static int hm_topk_impl(hm_engine* e, float c, float thr, int64_t k, int64_t row
         // emitted every candidate and so knows their number
         *count = (!want_count && k > 0 && total >= k) ? -1 : total;
         kk = (uint32_t)std::min<int64_t>(k, valid);
-        if (kk == 0 || !res) { e->prev_valid = false; return HM_OK; }
+        if (kk == 0 || !res) { e->st.drop_prev(); return HM_OK; }
         const uint32_t m = (uint32_t)std::min<uint64_t>(e->h->ctr64[2], e->ent_cap);
         rc = hm_select_sorted(e, res, e->ent2, m, kk, s);
         if (rc) return rc;
@@ -1022,32 +991,32 @@ extern "C" int hm_pairwise_topk_nocount(hm_engine* e, float c, float thr, int64_
 extern "C" int hm_topk_refresh_begin(hm_engine* e, float c, float thr, int64_t k, void* stream)
 {
     if (!e) return hm_fail(nullptr, HM_E_ARG, "hm_topk_refresh_begin: engine is NULL");
-    if (e->refresh_pending) return hm_fail(e, HM_E_STATE, "hm_topk_refresh_begin: a refresh is already pending");
+    if (e->st.refresh().pending) return hm_fail(e, HM_E_STATE, "hm_topk_refresh_begin: a refresh is already pending");
     if (!(c > 0.0f) || k <= 0 || k > (int64_t)e->sorted_cap) return hm_fail(e, HM_E_ARG, "hm_topk_refresh_begin: bad arguments");
     if (!hm_topk_incremental_ok(e, c, thr, k)) return HM_E_NA;                     // (no message: "not applicable" is an ordinary answer)
     HM_HIP(hipSetDevice(e->device));
-    e->armed = false;
+    e->st.disarm();
     const int rc = hm_topk_incremental_enqueue(e, c, thr, k, (hipStream_t)stream);
     if (rc) return rc;
-    e->refresh_pending = true;
-    e->refresh_k = k; e->refresh_c = c; e->refresh_thr = thr; e->refresh_stream = stream;
+    e->st.refresh_begin(k, c, thr, stream);
     return HM_OK;
 }
 
 extern "C" int hm_topk_refresh_end(hm_engine* e, float* d_out, int32_t* i_out, int32_t* j_out, int64_t* n_out)
 {
     if (!e) return hm_fail(nullptr, HM_E_ARG, "hm_topk_refresh_end: engine is NULL");
-    if (!e->refresh_pending) return hm_fail(e, HM_E_STATE, "hm_topk_refresh_end: no refresh pending");
+    if (!e->st.refresh().pending) return hm_fail(e, HM_E_STATE, "hm_topk_refresh_end: no refresh pending");
     if (!d_out || !i_out || !j_out || !n_out) return hm_fail(e, HM_E_ARG, "hm_topk_refresh_end: NULL output pointer");
     HM_HIP(hipSetDevice(e->device));
-    e->refresh_pending = false;
-    hipStream_t s = (hipStream_t)e->refresh_stream;
+    e->st.refresh_end();                                                           // (first: an HM_E_CAPACITY answer ends it too)
+    const SearchState::Refresh& r = e->st.refresh();
+    hipStream_t s = (hipStream_t)r.stream;
     *n_out = 0;
     uint32_t kk = 0;
-    const int rc = hm_topk_incremental_finish(e, e->refresh_k, s, &kk);
+    const int rc = hm_topk_incremental_finish(e, r.k, s, &kk);
     if (rc) return rc;                                                             // HM_E_CAPACITY: run hm_pairwise_topk_nocount instead
     HM_HIP(hipMemcpyAsync(e->d_prev, e->sorted, sizeof(uint4) * kk, hipMemcpyDeviceToDevice, s));
-    hm_topk_publish(e, kk, e->refresh_k, e->refresh_c, e->refresh_thr, true, d_out, i_out, j_out, n_out);
+    hm_topk_publish(e, kk, r.k, r.c, r.thr, true, d_out, i_out, j_out, n_out);
     return HM_OK;
 }
 
@@ -1055,16 +1024,14 @@ extern "C" int hm_pairwise_count(hm_engine* e, float c, float thr, int64_t n_lim
 {
     if (!e) return hm_fail(nullptr, HM_E_ARG, "hm_pairwise_count: engine is NULL");
     if (!count || !(c > 0.0f)) return hm_fail(e, HM_E_ARG, "hm_pairwise_count: bad arguments");
-    e->armed = false;
+    e->st.disarm();
     HM_HIP(hipSetDevice(e->device));
     *count = 0;
     int64_t valid = 0, total = 0;
     uint4* res = nullptr;
-    const bool had_cut = e->have_cut;             // a count does not disturb the cut prediction of the refreshes
-    const uint32_t cb = e->last_cut_bits; const int64_t ck = e->last_cut_k; const float cc = e->last_cut_c;
-    e->have_cut = false;
+    const SearchState::Cut cut = e->st.suspend_cut();     // a count does not disturb the cut prediction of the refreshes
     int rc = hm_topk_core(e, c, thr, 0, 0, -1, false, true, n_limit, &valid, &total, &res, (hipStream_t)stream);
-    e->have_cut = had_cut; e->last_cut_bits = cb; e->last_cut_k = ck; e->last_cut_c = cc;
+    e->st.restore_cut(cut);
     if (rc) return rc;
     *count = total;
     return HM_OK;
@@ -1127,8 +1094,8 @@ static int hm_candidates_by_rows(hm_engine* e, float c, float thr, int64_t row_b
 extern "C" int hm_pairwise_candidates(hm_engine* e, float c, float thr, int64_t row_begin, int64_t row_end, int64_t cap,
                                       int32_t* i_out, int32_t* j_out, float* d_out, int64_t* total, void* stream)
 {
-    if (e) e->armed = false;
     if (!e) return hm_fail(nullptr, HM_E_ARG, "hm_pairwise_candidates: engine is NULL");
+    e->st.disarm();
     if (!total || cap < 0 || (cap > 0 && (!i_out || !j_out || !d_out)))
         return hm_fail(e, HM_E_ARG, "hm_pairwise_candidates: bad output pointers");
     if (!(c > 0.0f)) return hm_fail(e, HM_E_ARG, "hm_pairwise_candidates: curvature must be > 0");
@@ -1149,8 +1116,8 @@ extern "C" int hm_pairwise_candidates(hm_engine* e, float c, float thr, int64_t 
 extern "C" int hm_row_argmin(hm_engine* e, int64_t row, int64_t n_partners, float c, float thr, float* d, int32_t* i, int32_t* j,
                              int32_t* found, void* stream)
 {
-    if (e) e->armed = false;
     if (!e) return hm_fail(nullptr, HM_E_ARG, "hm_row_argmin: engine is NULL");
+    e->st.disarm();
     if (!d || !i || !j || !found) return hm_fail(e, HM_E_ARG, "hm_row_argmin: NULL output pointer");
     if (row < 0 || row >= e->n || n_partners < 0 || n_partners > e->n || !(c > 0.0f))
         return hm_fail(e, HM_E_ARG, "hm_row_argmin: bad arguments");

@@ -79,6 +79,9 @@ def _walk(seed, n0, d, mode, form, knobs=()):
         # a walk in which the engine never took the incremental route on a grown table tests nothing of that route: that
         # would be a defect of motif D's parameters (thresholds, k), not of the engine
         assert sum(grown) >= 1
+    # every voiding call of motif E makes the incremental route inapplicable by construction: a refresh accepted after one
+    # means a transition forgot to void the cut or the previous list, whether or not a wrong result happens to follow
+    assert sum(voided) == 0
     return side
 
 
