@@ -57,6 +57,7 @@ EXPORTED_SYMBOLS = (
     "hm_rsgd_step", "hm_radam_step",
     "hm_edge_loss_fwd", "hm_edge_loss_bwd", "hm_debug_edge_loss_form", "hm_negsample_create", "hm_negsample_destroy", "hm_negsample_check_csr",
     "hm_negsample_set_csr", "hm_negsample_sample",
+    "hm_centroid_fwd", "hm_centroid_bwd", "hm_debug_centroid_form",
 )
 
 
@@ -200,6 +201,9 @@ def load() -> C.CDLL:
     L.hm_edge_loss_fwd.argtypes = [vp, i64, i64, C.c_int, vp, i64, i64, f32, vp, vp, vp]
     L.hm_edge_loss_bwd.argtypes = [vp, i64, i64, C.c_int, vp, i64, i64, f32, vp, vp, vp, vp, vp]
     L.hm_debug_edge_loss_form.argtypes = [C.c_int]
+    L.hm_centroid_fwd.argtypes = [vp, i64, i64, C.c_int, vp, i64, vp, vp, vp, i64, vp, vp, vp]
+    L.hm_centroid_bwd.argtypes = [vp, i64, i64, C.c_int, vp, i64, vp, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp]
+    L.hm_debug_centroid_form.argtypes = [C.c_int]
     L.hm_negsample_create.argtypes = [C.POINTER(vp), C.c_int]
     L.hm_negsample_destroy.argtypes = [vp]
     L.hm_negsample_check_csr.argtypes = [vp, vp, i64]

@@ -139,6 +139,39 @@ class BatchEncoder:
         np.cumsum(lens, out=offsets[1:])
         return ids, offsets
 
+    def encode_device(self, texts: Sequence[str]) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        """``encode`` of every line, left on the device: (ids int64 [T], offsets int64 [n + 1], lengths int32 [n]).
+
+        This is the slab of ``run``: line ``k`` owns the span ``offsets[k] : offsets[k + 1]`` (its characters, so ``T`` is the
+        number of characters of the batch), its ``lengths[k]`` ids stand at the front of the span and the slack behind them
+        holds ``-1``.  Symbols are mapped to vocabulary rows by a device copy of the table ``encode_arrays`` uses, unknown
+        ones to ``unk``.  Nothing is read back: the only transfer is the upload of the text.  The layout is the one
+        ``embedding.pooling.lorentz_centroid`` consumes."""
+        n = len(texts)
+        if n == 0:
+            return (torch.zeros(0, dtype=torch.int64, device=self.device), torch.zeros(1, dtype=torch.int64, device=self.device),
+                    torch.zeros(0, dtype=torch.int32, device=self.device))
+        sym_h, off_h = self.symbols(texts)
+        if np.diff(off_h).max() >= 2 ** 31:
+            raise ValueError("a line of 2^31 or more characters")
+        with torch.cuda.device(self.device):
+            if getattr(self, "_sym2vocab_dev", None) is None:
+                self._sym2vocab_dev = torch.from_numpy(self._sym2vocab).to(self.device)
+            s2v, total = self._sym2vocab_dev, int(off_h[-1])
+            sym = torch.from_numpy(sym_h).to(self.device)
+            off = torch.from_numpy(off_h).to(self.device)
+            lens = off[1:] - off[:-1]
+            order = torch.argsort(lens, descending=True, stable=True)
+            out, out_len, _ = self.run(sym, off, order)
+            pos = torch.arange(total, device=self.device) - torch.repeat_interleave(off[:-1], lens, output_size=total)
+            keep = pos < torch.repeat_interleave(out_len.to(torch.int64), lens, output_size=total)
+            ids = torch.full((total,), self.unk, dtype=torch.int64, device=self.device)
+            if s2v.numel():
+                known = keep & (out >= 0) & (out < s2v.numel())
+                ids = torch.where(known, s2v[out.clamp(0, s2v.numel() - 1).long()], ids)
+            ids = torch.where(keep, ids, torch.full_like(ids, -1))
+        return ids, off, out_len
+
     def encode_batch(self, texts: Sequence[str]) -> List[List[int]]:
         ids, offsets = self.encode_arrays(texts)
         lst = ids.tolist()

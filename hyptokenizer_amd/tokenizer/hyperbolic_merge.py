@@ -501,6 +501,20 @@ class HyperbolicTokenizer:
         """``[self.encode(t) for t in texts]`` in one kernel launch."""
         return self._batch_encoder().encode_batch(texts)
 
+    def embed_batch(self, texts: List[str], weights: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """One point of the hyperboloid per line, ``[len(texts), d + 1]``: the Lorentz centroid
+        (``embedding.pooling.lorentz_centroid``) of the embedding rows of the line's tokens, tokenized, mapped and pooled on
+        the device.  An empty line gives the origin.  ``weights`` (optional, fp32 on the device) holds one weight per
+        position of ``BatchEncoder.encode_device``'s slab, i.e. per character of the batch, read at the front of every
+        line's span.  Differentiable in ``self.embeddings`` (sparse gradient).  Needs ``sign_convention="lorentz"``."""
+        if self.sign_convention != "lorentz":
+            raise ValueError("embed_batch: the Lorentz centroid is defined under sign_convention='lorentz' only, this tokenizer "
+                             f"uses {self.sign_convention!r}")
+        from ..embedding.pooling import lorentz_centroid
+        ids, offsets, lengths = self._batch_encoder().encode_device(texts)
+        # ids name live rows only (token2idx), so the whole pre-allocated table is passed and the gradient has its shape
+        return lorentz_centroid(self.embeddings, ids, offsets, lengths, weights, validate=False)
+
     def corpus_statistics(self, texts: List[str]):
         """Token, character, word-boundary, morpheme and sub-word counts of ``texts`` (tokenizer/corpus_stats.py): the
         integers behind scripts/compare_tokenizers.py's metrics, counted on the GPU without a token reaching the host."""

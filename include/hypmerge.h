@@ -666,6 +666,36 @@ int hm_edge_loss_bwd(const float* x_dev, int64_t ld, int64_t table_rows, int d1,
  * partners); d_0 and every u_k are the same bits. */
 int hm_debug_edge_loss_form(int form);
 
+/* ---- Lorentz-centroid pooling of token rows ---------------------------------------------------------------
+ * Serves embedding.pooling.lorentz_centroid / HyperbolicEmbeddingBag and HyperbolicTokenizer.embed_batch: one point of the
+ * hyperboloid per line from the rows of its tokens (Law et al., ICML 2019).  x [table_rows, ld] fp32 points of the unit
+ * hyperboloid (d1 columns, 2 <= d1 <= 129), ids int64 [t], offsets int64 [n + 1] non-decreasing within [0, t] (clamped into
+ * it otherwise), lengths int32 [n] or NULL (clamped to the span), weights fp32 [t] or NULL, all on the device.  Segment i is
+ * ids[offsets[i] : offsets[i] + len_i]; a token is live when it lies inside that length and its id lies in [0, table_rows)
+ * (-1 is the documented padding); nothing else is dereferenced.
+ *   s_i = sum_t w_t x_{ids[t]},  q_i = s_i0^2 - |s_is|^2,  mu_i = s_i / sqrt(q_i);  without a live token, or where q_i is not
+ *   positive and finite, mu_i = (1, 0, .., 0) and the segment's gradient is zero.
+ * hm_centroid_fwd writes mu_dev [n, d1] and inv_nu_dev [n] = 1 / sqrt(q_i) (0 for a degenerate segment), the only state
+ * between the two calls.  hm_centroid_bwd takes grad_dev [n, d1] and, with h_i = (g_i + (g_i . mu_i) J mu_i) / sqrt(q_i),
+ * J = diag(-1, 1, .., 1), writes the Euclidean gradient in COO form, position order: values_dev [t, d1] row p = w_p h_i and
+ * coo_dev int64 [t] = ids[p]; a skipped position (slack behind a length, id out of range, outside every span) has index 0 and
+ * a zero row.  grad_weights_dev [t] (or NULL: then no table row is read) receives h_i . x_{ids[p]}, 0 where skipped.  Every
+ * row is written once, no atomics: two calls on the same inputs give the same bits.  Engine-independent; errors through
+ * hm_last_error(NULL); asynchronous on `stream`.  HM_E_ARG before the device is touched for a NULL table, d1 outside 2..129,
+ * ld < d1, negative table_rows / t / n, NULL offsets with n > 0, NULL ids with t > 0.  n == 0: the forward launches nothing,
+ * the backward zero-fills its outputs.  Replaces: nothing the reference runs (it has no pooling). */
+int hm_centroid_fwd(const float* x_dev, int64_t ld, int64_t table_rows, int d1, const int64_t* ids_dev, int64_t t,
+                    const int64_t* offsets_dev, const int32_t* lengths_dev, const float* weights_dev, int64_t n, float* mu_dev,
+                    float* inv_nu_dev, void* stream);
+int hm_centroid_bwd(const float* x_dev, int64_t ld, int64_t table_rows, int d1, const int64_t* ids_dev, int64_t t,
+                    const int64_t* offsets_dev, const int32_t* lengths_dev, const float* weights_dev, int64_t n, const float* mu_dev,
+                    const float* inv_nu_dev, const float* grad_dev, float* values_dev, int64_t* coo_dev, float* grad_weights_dev,
+                    void* stream);
+/* Test / tuning hook: the work decomposition of the two calls above from now on -- 0: one lane group per segment, 1: one wave
+ * per segment, -1: chosen per call from n and the mean segment length (the default).  Results agree to
+ * rounding (another order of the sum over the tokens of a segment). */
+int hm_debug_centroid_form(int form);
+
 /* Negative sampler.  The graph is a symmetric CSR as for hm_graph_set_csr (HOST arrays, 1 <= n < 2^31) whose rows are
  * additionally sorted and free of repeats (HM_E_ARG otherwise; hm_negsample_check_csr is that check alone and touches no
  * device).  hm_negsample_sample: pairs_dev int64 [n_pairs, 2] -> out_dev int64 [n_pairs, 2 + k], columns 0 and 1 copied,
