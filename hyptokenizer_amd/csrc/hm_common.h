@@ -74,6 +74,9 @@ typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 #define HM_PART_SLOTS 256          // partial records (>= HM_TAIL_BLOCKS, HM_ROWPASS_BLOCKS)
 #define HM_LOOP_MAX_STEPS 256      // steps one device-resident loop call may enqueue
 #define HM_BATCH_MAX 4096          // merges per hm_merge_append_batch_host call
+#ifndef HM_SCAN_HEAD
+#define HM_SCAN_HEAD 3             // k-steps of the argmin scan's head test (hm_head_steps below; 3 against 4, two builds interleaved on one box: 0.177 against 0.198 ms per step at 50 000 rows)
+#endif
 
 // prefilter forms (hm_engine_create / hm_set_prefilter)
 #define HM_PREFILTER_AUTO 0
@@ -156,6 +159,11 @@ struct ScanArgs {
     int n_items;
     unsigned long long q_tag;
     unsigned long long* q_ctr;
+    // head test (hm_scan.hip, HEAD > 0): a word in pinned host memory.  The head kernel pays when the bound is tight (a
+    // group is done after HEAD of its k-steps) and costs HEAD extra k-steps per group when it is loose (every group is
+    // recomputed); the HOST picks the kernel per launch (hm_head_live) and a head kernel whose waves had to recompute most
+    // of their groups writes 1 here, which sends the following launches back to the kernel without the test.
+    uint32_t* head_bad;
     // ARGMIN mode: shift amounts of the engine's running-key layout (hm_key_low); read by the wide-key kernels only
     int key_wide;                 // host-side: the engine's key has more than 17 row-index bits
     int key_si, key_sj;
@@ -177,6 +185,7 @@ struct HostCtl {                 // pinned host mirror of small device results
     ArgminRec loop_recs[HM_LOOP_MAX_STEPS];
     uint32_t hist[HM_DIGIT_BINS];
     unsigned long long xhist[HM_EXACT_BINS];   // hm_exact.hip: one bin can hold more than 2^32 pairs (a tie flood)
+    uint32_t head_bad;           // written by the head kernels themselves (ScanArgs::head_bad), read by hm_head_live
 };
 
 // state of the device-resident merge loops (one per engine, in HBM)
@@ -213,6 +222,9 @@ struct hm_engine {
     std::map<const void*, int> scan_slots; // resident blocks per scan kernel instantiation on this engine's device
     int force_shape = -1;                 // HM_TUNE_SHAPE: bf16 block shape of every launch (tuning builds)
     int64_t big_min_rows = 80000;         // bf16 form: launches covering at least the pairs of this many rows use 512-row blocks
+    int head = HM_SCAN_HEAD;              // knob `head`: k-steps of the argmin scan's head test (hm_head_steps); 0 = the kernels without it
+    bool head_force = false;              // knob `head_force` (tests): every eligible argmin launch takes the head kernel, whatever hm_head_live expects
+    int64_t head_merges = 0;              // merged rows appended since the table was set or an existing row changed (hm_head_live)
     int64_t max_rows = 0, rows_alloc = 0, n = 0;
     int d1 = 0, d = 0, NG = 0, RS = 0, sign_mode = 0;
     float* img = nullptr;
@@ -250,7 +262,10 @@ struct hm_engine {
     // software-pipelined standard loop: a second (high-priority) stream for the step's tail work, which then runs under
     // the NEXT step's scan; per buffer set an event behind the scan and one behind the tail; the new row's key per set
     bool pipeline = true;
-    int64_t pipeline_min_pairs = 800000000ll;   // (knob "pipeline_pairs"): ~40 000 rows -- a scan of 150 us against 50 us of tail work under it
+    // (knob "pipeline_pairs"): ~30 000 rows, the smallest size measured.  With the head kernel a scan takes 87 / 103 / 122 / 141-163 /
+    // 168 us at 30 / 35 / 40 / 45 / 50 thousand rows; pipelined against sequential, interleaved: 0.099 / 0.115 / 0.132 / 0.163 /
+    // 0.178 ms per step against 0.118 / 0.128 / 0.146 / 0.166 / 0.191, no batch aborted by the order guard
+    int64_t pipeline_min_pairs = 450000000ll;
     int pipe_fault_at = -1;              // test hook (knob "pipe_fault_at"): the scan of this step of the next batch is made to trip its order guard
     hipStream_t aux = nullptr;
     hipEvent_t ev_scan[2] = {nullptr, nullptr}, ev_tail[2] = {nullptr, nullptr}, ev_join = nullptr;
@@ -300,6 +315,22 @@ int hm_fail(hm_engine* e, int code, const std::string& msg);
 // rows from first_changed_row on were written: when that is an existing row, the state that rests on the old rows is void
 // (SearchState::row_changed) and the argmin seed is zeroed on the stream
 int hm_rows_changed(hm_engine* e, int64_t first_changed_row, hipStream_t s);
+// Which argmin kernel a launch gets.  The loops keep merged rows in the table, so from the third merge on the nearest pair is
+// a (parent, midpoint) pair and the scan's bound sits far below the bulk of the pairs: the head kernel.  A fresh table, a
+// table whose rows were edited, or one on which a head kernel reported a loose bound (HostCtl::head_bad): the kernel
+// without the test, unchanged.  A heuristic on the speed only -- both kernels return the same entries' minimum.
+// Limits of the hint: head_bad is read here, when a launch is ENQUEUED, with no ordering against the kernels that write it, so
+// a loop that has already enqueued a batch (up to HM_LOOP_MAX_STEPS launches) of head kernels on a loose bound runs the whole
+// batch through them (about five times the scan time each) before the host sees the word; and it is sticky -- one loose
+// search, for example an argmin with a much lower threshold between two loops, sends every later launch to the HEAD = 0
+// kernel until hm_head_reset (set_table, an edit of an existing row, hm_truncate).  The HEAD = 0 kernels do not report
+// back, so nothing clears it earlier.
+inline bool hm_head_live(const hm_engine* e)
+{
+    if (e->head == 0) return false;
+    return e->head_force || (e->head_merges >= 3 && e->h != nullptr && e->h->head_bad == 0u);
+}
+inline void hm_head_reset(hm_engine* e) { e->head_merges = 0; if (e->h) e->h->head_bad = 0u; }
 // statistics of one search (hm_last_scan_stats): begin takes in a pending device-side timing and zeroes them; add reads the
 // engine's event pair (ev0, ev1) behind a synchronised scan of `pairs` pairs
 void hm_scan_stats_begin(hm_engine* e);
@@ -553,21 +584,90 @@ __device__ __forceinline__ uint32_t hm_pack_bf16(float lo, float hi)
     return (uint32_t)__builtin_bit_cast(unsigned short, a) | ((uint32_t)__builtin_bit_cast(unsigned short, b) << 16);
 }
 
+// ---- the head set of the argmin scan's early stop (hm_scan.hip) ----
+// A bf16 row is walked in k-steps of two chunks (16 K-slots; an odd chunk count ends on a half step).  The HEAD of a row is
+// the k-step that holds the time slots (the last one) plus the first HM_SCAN_HEAD - 1 k-steps; the REST is every spatial
+// K-slot in between, [hm_rest_begin, hm_rest_end).  The scan kernel and the rest norm in the row's last K-slot
+// (hm_rest_norm_bf16) are both derived from these four functions and from nothing else.  A row with fewer than
+// HM_SCAN_HEAD + 1 k-steps has no head (0): nothing would be skipped.
+__host__ __device__ constexpr int hm_bf16_ksteps(int KC) { return (KC + 1) / 2; }
+__host__ __device__ constexpr int hm_head_steps(int KC) { return hm_bf16_ksteps(KC) >= HM_SCAN_HEAD + 1 ? HM_SCAN_HEAD : 0; }
+// k-step walked as the k-th of the head: the one with the time slots first, then 0, 1, ...
+__host__ __device__ constexpr int hm_head_kstep(int k, int ksteps) { return k == 0 ? ksteps - 1 : k - 1; }
+__host__ __device__ constexpr int hm_rest_begin(int KC) { return hm_head_steps(KC) ? 16 * (hm_head_steps(KC) - 1) : 0; }
+__host__ __device__ constexpr int hm_rest_end(int KC) { return hm_head_steps(KC) ? 16 * (hm_bf16_ksteps(KC) - 1) : 0; }
+
+// r^ of a row: a bf16 value (returned as its 16 bits) that is >= the Euclidean norm of the row's bf16-ROUNDED spatial entries
+// in the rest slots.  The squares of bf16 values are exact in double and cannot leave its range; the sum of at most 128 of
+// them and the square root carry a relative error below 40 * 2^-53, which the factor (1 + 2^-40) covers; the result is
+// then rounded UP to bf16.  Always finite (clamped to the largest finite bf16: a row whose rest norm is larger has no
+// finite x0); never a subnormal (the matrix cores may flush those: a non-zero norm is at least the smallest normal);
+// NaN only when a rest entry is NaN.
+__device__ __forceinline__ uint32_t hm_rest_norm_round(double t)
+{
+    const double rn = sqrt(t) * (1.0 + 0x1p-40);
+    if (rn != rn) return 0x7fc0u;
+    if (!(rn > 0.0)) return 0u;
+    uint32_t b = hm::fbits((float)rn) >> 16;                           // truncated: at or below (float)rn
+    if ((double)hm::bitsf(b << 16) < rn) ++b;                          // the next bf16 is above (float)rn + one fp32 ulp >= rn
+    if (b > 0x7f7fu) b = 0x7f7fu;
+    if (b < 0x0080u) b = 0x0080u;
+    return b;
+}
+__device__ __forceinline__ double hm_rest_sq(const float* spatial, int s)
+{
+    const double v = (double)(float)(__bf16)spatial[s];
+    return v * v;
+}
+// one thread: four interleaved sums (accumulator q takes the rest slots s = s0 + q, s0 + q + 4, ...; s0 is a multiple of 16),
+// combined as (0 + 1) + (2 + 3)
+__device__ __forceinline__ uint32_t hm_rest_norm_bf16(const float* spatial /* x[1..d] */, int d, int KC)
+{
+    const int s0 = hm_rest_begin(KC), s1 = hm_rest_end(KC) < d ? hm_rest_end(KC) : d;
+    double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
+    int s = s0;
+    for (; s + 4 <= s1; s += 4) {
+        const double q0 = hm_rest_sq(spatial, s), q1 = hm_rest_sq(spatial, s + 1), q2 = hm_rest_sq(spatial, s + 2), q3 = hm_rest_sq(spatial, s + 3);
+        a0 = a0 + q0; a1 = a1 + q1; a2 = a2 + q2; a3 = a3 + q3;
+    }
+    if (s < s1) a0 = a0 + hm_rest_sq(spatial, s);
+    if (s + 1 < s1) a1 = a1 + hm_rest_sq(spatial, s + 1);
+    if (s + 2 < s1) a2 = a2 + hm_rest_sq(spatial, s + 2);
+    return hm_rest_norm_round((a0 + a1) + (a2 + a3));
+}
+// the same value, bit for bit, by a whole wave (all 64 lanes call; result on every lane): lanes 0..3 own one of the four
+// sums each -- a quarter of the chain -- and the combine runs over shuffles
+__device__ __forceinline__ uint32_t hm_wave_rest_norm_bf16(const float* spatial /* x[1..d] */, int d, int KC, int lane)
+{
+    const int s0 = hm_rest_begin(KC), s1 = hm_rest_end(KC) < d ? hm_rest_end(KC) : d;
+    double a = 0.0;
+    if (lane < 4)
+        for (int s = s0 + lane; s < s1; s += 4) a = a + hm_rest_sq(spatial, s);
+    const double a0 = __shfl(a, 0, 64), a1 = __shfl(a, 1, 64), a2 = __shfl(a, 2, 64), a3 = __shfl(a, 3, 64);
+    return hm_rest_norm_round((a0 + a1) + (a2 + a3));
+}
+
 // chunk c (K-slots 8c .. 8c+7) of a bf16 image row; the LAST FOUR slots of the row hold the time coordinate
-// split as x0 ~ hi + lo: streamed (B) encoding [hi, lo, hi, 0]; the stationary (A) side rewrites its copy in
-// registers to [-hi, -hi, -lo, 0], so the MFMA adds -(hi*hi' + hi*lo' + lo*hi') = -x0*y0 (1 + O(2^-16)).
-__device__ __forceinline__ uint4 hm_bf16_chunk(const float* spatial /* x[1..d] */, float x0, int d, int KC, int c)
+// split as x0 ~ hi + lo and the rest norm r^ (above): streamed (B) encoding [hi, lo, hi, r^]; the stationary (A) side
+// rewrites its copy in registers to [-hi, -hi, -lo, 0], so the MFMA adds -(hi*hi' + hi*lo' + lo*hi') = -x0*y0 (1 + O(2^-16))
+// and 0 * r^ = 0 (r^ is finite).  Only the head test of the argmin scan puts its own r^ into the fourth slot.
+// (`rhat`: the row's rest norm as bf16 bits -- hm_rest_norm_bf16 or its wave form; read for the last chunk only)
+__device__ __forceinline__ uint4 hm_bf16_chunk(const float* spatial /* x[1..d] */, float x0, int d, int KC, int c, uint32_t rhat)
 {
     float f[8];
 #pragma unroll
     for (int q = 0; q < 8; ++q) { const int sidx = 8 * c + q; f[q] = sidx < d ? spatial[sidx] : 0.0f; }
+    uint32_t w3;
     if (c == KC - 1) {
         const __bf16 hb = (__bf16)x0;
         const float hi = (float)hb;
         const float lo = x0 - hi;
-        f[4] = hi; f[5] = lo; f[6] = hi; f[7] = 0.0f;
+        f[4] = hi; f[5] = lo;
+        w3 = (hm_pack_bf16(hi, 0.0f) & 0xffffu) | (rhat << 16);
+    } else {
+        w3 = hm_pack_bf16(f[6], f[7]);
     }
-    return make_uint4(hm_pack_bf16(f[0], f[1]), hm_pack_bf16(f[2], f[3]), hm_pack_bf16(f[4], f[5]), hm_pack_bf16(f[6], f[7]));
+    return make_uint4(hm_pack_bf16(f[0], f[1]), hm_pack_bf16(f[2], f[3]), hm_pack_bf16(f[4], f[5]), w3);
 }
 
 __device__ __forceinline__ unsigned long long hm_wave_min_u64(unsigned long long v)

@@ -41,7 +41,7 @@ extern "C" int hm_abi_version(void) { return HM_ABI_VERSION; }
 // ---- work-decomposition knobs (test / tuning hook: hm_debug_set_knob, hm_debug_set_default_knob) ----
 #if defined(HM_TUNING)
 static const char* const kKnobNames[] = {"chunk", "tail", "tail_div", "big_rows", "shape", "incr_topk", "kc_even", "phases", "ph_share0", "ph_share1", "ph_share2", "ph_share3", "ph_share4",
-                                        "ph_div1", "ph_div2", "ph_div3", "ph_div4", "ph_div5", "pipeline", "pipe_fault_at", "pipeline_pairs", "dyn", "dyn_slots"};
+                                        "ph_div1", "ph_div2", "ph_div3", "ph_div4", "ph_div5", "pipeline", "pipe_fault_at", "pipeline_pairs", "dyn", "dyn_slots", "head", "head_force"};
 #endif
 static std::map<std::string, double> g_default_knobs;          // applied to every engine created afterwards
 
@@ -58,6 +58,8 @@ static int hm_apply_knob(hm_engine* e, const char* name, double v)
     else if (k.size() == 9 && k.compare(0, 8, "ph_share") == 0 && k[8] >= '0' && k[8] < '0' + HM_SCAN_PHASES - 1) { if (!(v >= 0.0 && v <= 1.0)) return HM_E_ARG; e->ph_share[k[8] - '0'] = v; }
     else if (k.size() == 7 && k.compare(0, 6, "ph_div") == 0 && k[6] >= '1' && k[6] < '0' + HM_SCAN_PHASES) { if (!(v >= 1 && v <= 64)) return HM_E_ARG; e->ph_div[k[6] - '0'] = (int)v; }
     else if (k == "dyn_slots") { if (!(v >= 0 && v <= 65536)) return HM_E_ARG; e->dyn_slots = (int)v; }
+    else if (k == "head") { if (!(v == 0.0 || v == (double)HM_SCAN_HEAD)) return HM_E_ARG; e->head = (int)v; }      // argmin scan, bf16 form: 0 = no head test
+    else if (k == "head_force") e->head_force = v != 0.0;
     else if (k == "dyn") e->dyn_queue = v != 0.0;           // scan: resident grid + in-order item queue instead of one block per item
     else if (k == "pipeline") e->pipeline = v != 0.0;       // standard loop: the step's tail work under the next step's scan (0: strictly sequential)
     else if (k == "pipe_fault_at") e->pipe_fault_at = (int)v;
@@ -144,6 +146,7 @@ static int hm_engine_alloc(hm_engine* e)
     HM_HIP(hipMalloc(&e->d_parts, sizeof(ArgminPart) * HM_PART_SLOTS));
     HM_HIP(hipMalloc(&e->d_hist, sizeof(uint32_t) * HM_DIGIT_BINS));
     HM_HIP(hipHostMalloc(&e->h, sizeof(HostCtl), hipHostMallocDefault));
+    memset(e->h, 0, sizeof(HostCtl));
     HM_HIP(hipHostMalloc(&e->h_sorted, sizeof(uint4) * (size_t)e->sorted_cap, hipHostMallocDefault));
     // timing events without the system-scope fence a default event adds around the scan
     HM_HIP(hipEventCreateWithFlags(&e->ev0, hipEventDisableSystemFence));
@@ -271,6 +274,7 @@ extern "C" int hm_set_table(hm_engine* e, const float* X_dev, int64_t ld, int64_
     if (rc) return rc;
     e->n = n_rows;
     e->st.table_replaced();
+    hm_head_reset(e);
     HM_HIP(hipMemsetAsync(e->d_seed, 0, sizeof(ArgminSeed), s));      // new table: no seed
     return HM_OK;
 }
@@ -294,6 +298,7 @@ int hm_rows_changed(hm_engine* e, int64_t first_changed_row, hipStream_t s)
 {
     if (first_changed_row < e->n) {          // an existing row changed: cut prediction, argmin seed and arming are void
         e->st.row_changed();
+        hm_head_reset(e);
         HM_HIP(hipMemsetAsync(e->d_seed, 0, sizeof(ArgminSeed), s));
     }
     return HM_OK;

@@ -42,6 +42,7 @@ extern "C" int hm_truncate(hm_engine* e, int64_t n_rows, void* stream)
     }
     if (const int rc = hm_rows_changed(e, n_rows, s)) return rc;      // rows were removed: as if they had changed
     e->n = n_rows;
+    hm_head_reset(e);
     return HM_OK;
 }
 
@@ -154,7 +155,7 @@ static int hm_std_merge_steps_pipelined(hm_engine* e, float c, float thr, const 
 {
     int rc = hm_pipeline_init(e);
     if (rc) return rc;
-    const int64_t n0 = e->n;
+    const int64_t n0 = e->n, hm0 = e->head_merges;
     const float sqrt_c = sqrtf(c);
     hipStream_t sb = e->aux;
     // the tail stream starts behind everything the caller's stream holds so far (table, token lengths, loop state)
@@ -167,6 +168,7 @@ static int hm_std_merge_steps_pipelined(hm_engine* e, float c, float thr, const 
     for (int64_t k = 0; k < steps; ++k) {
         const int set = (int)(k & 1);
         e->n = n0 + k;                                   // rows of step k's table (optimistic: corrected by the caller when the batch stops early)
+        e->head_merges = hm0 + k;                        // (which argmin kernel this step's scan gets: hm_head_live)
         const int64_t n_old = k == 0 ? e->n : e->n - 1;  // scan_old(k): all rows but the newest (step 0: the whole table)
         ScanArgs a; dim3 grid;
         if (!hm_prepare_scan(e, b, 0, -1, a, grid, n_old)) return hm_fail(e, HM_E_STATE, "hm_std_merge_steps: empty scan");
@@ -221,6 +223,7 @@ static int hm_std_merge_steps_pipelined(hm_engine* e, float c, float thr, const 
         HM_HIP(hipEventRecord(e->ev_tail[set], sb));
     }
     e->n = n0 + steps;
+    e->head_merges = hm0;                                // (the caller counts the steps that merged)
     // the caller's stream continues behind the last tails
     HM_HIP(hipStreamWaitEvent(s, e->ev_tail[(steps - 1) & 1], 0));
     if (steps >= 2) HM_HIP(hipStreamWaitEvent(s, e->ev_tail[(steps - 2) & 1], 0));
@@ -248,7 +251,7 @@ extern "C" int hm_std_merge_steps(hm_engine* e, float c, float thr, float* X_dev
         for (int64_t k = 0; k < steps; ++k) { rec_out[4 * k] = k == 0 ? 0u : 3u; rec_out[4 * k + 1] = 0; rec_out[4 * k + 2] = rec_out[4 * k + 3] = 0xffffffffu; }
         return HM_OK;
     }
-    const int64_t n0 = e->n;
+    const int64_t n0 = e->n, hm0 = e->head_merges;
     const float sqrt_c = sqrtf(c);
     HM_HIP(hipMemsetAsync(e->d_loop, 0, sizeof(LoopState), s));
     bool armed = e->st.take_arm(0, -1);
@@ -257,11 +260,11 @@ extern "C" int hm_std_merge_steps(hm_engine* e, float c, float thr, float* X_dev
     if (time_all) hm_read_loop_events(e);         // the events are about to be reused
     int64_t all_pairs[HM_LOOP_MAX_STEPS];
     // pipelined when a scan is long against a tail kernel (the tail of step k - 2 has to be through while scan k - 1 runs; the
-    // scans' order guard catches the rest): from ~40 000 rows on
+    // scans' order guard catches the rest): from ~30 000 rows on (hm_engine::pipeline_min_pairs)
     const bool piped = e->pipeline && steps >= 2 && hm_pairs_in_range(e->n, 0, e->n - 1) >= e->pipeline_min_pairs;
     if (piped) {
         const int rcp = hm_std_merge_steps_pipelined(e, c, thr, b, X_dev, ld, steps, s, all_pairs, time_all, &timed_pairs);
-        if (rcp) { (void)hipStreamSynchronize(s); if (e->aux) (void)hipStreamSynchronize(e->aux); e->n = n0; return rcp; }
+        if (rcp) { (void)hipStreamSynchronize(s); if (e->aux) (void)hipStreamSynchronize(e->aux); e->n = n0; e->head_merges = hm0; return rcp; }
     }
     for (int64_t k = 0; k < (piped ? 0 : steps); ++k) {
         ScanArgs a; dim3 grid;
@@ -269,7 +272,7 @@ extern "C" int hm_std_merge_steps(hm_engine* e, float c, float thr, float* X_dev
         a.stop = &e->d_loop->stop;
         if (!armed) {
             int rc0 = hm_launch_seed_init(e, a, s);
-            if (rc0) { e->n = n0; return rc0; }
+            if (rc0) { e->n = n0; e->head_merges = hm0; return rc0; }
         }
         // the last scan of the batch carries the timing events (one event pair per engine); in the measurement mode of
         // hm_debug_time_loops every scan has its own pair
@@ -287,9 +290,10 @@ extern "C" int hm_std_merge_steps(hm_engine* e, float c, float thr, float* X_dev
         mf.X = X_dev; mf.ld = ld; mf.new_row = e->n; mf.c = c;
         mf.len = e->d_len; mf.len_rw = e->d_len; mf.loop = e->d_loop; mf.rec_ring = e->d_loop_recs + k;
         int rc = hm_launch_argmin_tail(e, a, sqrt_c, thr, e->d_rec, true, 0, 0x7fffffff, true, mf, s);
-        if (rc) { e->n = n0; return rc; }
+        if (rc) { e->n = n0; e->head_merges = hm0; return rc; }
         armed = true;
         e->n += 1;                            // optimistic: corrected below when the batch stopped early
+        e->head_merges += 1;
     }
     if (time_all) HM_HIP(hipEventRecord(e->loop_evs[2 * HM_LOOP_MAX_STEPS + 1], s));
     HM_HIP(hipMemcpyAsync(e->h->loop_recs, e->d_loop_recs, sizeof(ArgminRec) * (size_t)steps, hipMemcpyDeviceToHost, s));
@@ -297,6 +301,7 @@ extern "C" int hm_std_merge_steps(hm_engine* e, float c, float thr, float* X_dev
     HM_HIP(hipStreamSynchronize(s));
     hm_unpack_recs(e->h->loop_recs, steps, rec_out, done);
     e->n = n0 + *done;
+    e->head_merges = hm0 + *done;
     if (piped && *done < steps && e->h->ctr[7] == 5u) {
         // a scan's order guard tripped (never seen outside the test hook): the steps from there on, strictly sequentially
         e->st.disarm();

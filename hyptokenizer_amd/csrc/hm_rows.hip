@@ -71,7 +71,7 @@ __global__ void hm_build_image16_kernel(const float* __restrict__ X, int64_t ld,
         uint4 v = make_uint4(0, 0, 0, 0);
         const float* xr = X + row * ld;
         if (c >= KC) v.x = hm::fbits(xr[0]);
-        else v = hm_bf16_chunk(xr + 1, xr[0], d, KC, c);
+        else v = hm_bf16_chunk(xr + 1, xr[0], d, KC, c, c == KC - 1 ? hm_rest_norm_bf16(xr + 1, d, KC) : 0u);
         *reinterpret_cast<uint4*>(img16 + (row * CH + c) * 16) = v;
     }
 }
@@ -325,7 +325,9 @@ __global__ __launch_bounds__(64) void hm_project_table_kernel(float* __restrict_
                 const float hi = (float)hb, lo = x0 - hi;
                 uint32_t* slots = reinterpret_cast<uint32_t*>(r16 + (KC - 1) * 16 + 8);       // K-slots 8c+4 .. 8c+7 of the last chunk
                 slots[0] = hm_pack_bf16(hi, lo);
-                slots[1] = hm_pack_bf16(hi, 0.0f);
+                // the third slot only: the fourth holds the rest norm of the spatial part (hm_rest_norm_bf16), which a
+                // re-projection does not change
+                reinterpret_cast<unsigned short*>(slots)[2] = (unsigned short)(hm_pack_bf16(hi, 0.0f) & 0xffffu);
             }
         } else {
             r2 = 0.0f; x0 = 0.0f;
@@ -408,6 +410,7 @@ extern "C" int hm_merge_append(hm_engine* e, int32_t i, int32_t j, float w, floa
     HM_HIP(hipGetLastError());
     if (const int rc = hm_rows_changed(e, new_row, (hipStream_t)stream)) return rc;
     if (new_row + 1 > e->n) e->n = new_row + 1;
+    e->head_merges += 1;
     return HM_OK;
 }
 
@@ -429,6 +432,7 @@ extern "C" int hm_merge_append_batch(hm_engine* e, const int32_t* I_dev, const i
     HM_HIP(hipGetLastError());
     if (const int rc = hm_rows_changed(e, first_row, (hipStream_t)stream)) return rc;
     if (first_row + count > e->n) e->n = first_row + count;
+    e->head_merges += count;
     return HM_OK;
 }
 

@@ -91,10 +91,11 @@ __device__ __forceinline__ void hm_wave_store_row(MidScratch& ms, float r2, int 
         else ir[hm_img_off(k - 1)] = v;
     }
     const int CH = hm_row16_chunks(KC);
+    const uint32_t rhat = hm_wave_rest_norm_bf16(ms.so + 1, d, KC, lane);
     for (int cidx = lane; cidx < CH; cidx += 64) {
         uint4 v = make_uint4(0, 0, 0, 0);
         if (cidx >= KC) v.x = hm::fbits(ms.so[0]);
-        else v = hm_bf16_chunk(ms.so + 1, ms.so[0], d, KC, cidx);
+        else v = hm_bf16_chunk(ms.so + 1, ms.so[0], d, KC, cidx, rhat);
         *reinterpret_cast<uint4*>(img16 + ((int64_t)row * CH + cidx) * 16) = v;
     }
 }

@@ -81,7 +81,26 @@ __device__ __forceinline__ void hm_dma_run(const char* src, uint32_t dst)
 #define HM_SCAN_DEEP_PREFETCH 1
 #endif
 // WK (ARGMIN mode only): the engine's running key is wide -- shift amounts from ScanArgs; narrow: (i << 15) | (j >> 2)
-template <int NG, int SIGN, int MODE, int BF, int TM, int WPB, int SUB, bool WK = false>
+//
+// HEAD > 0 (bf16 form, lorentz sign, ARGMIN, two accumulator sets): the head test.  A pair's u is x0 y0 - sum_k x_k y_k;
+// with the spatial K-slots split into a head set H and the rest R (hm_head_steps / hm_rest_begin / hm_rest_end of
+// hm_common.h), Cauchy-Schwarz gives  u >= x0 y0 - sum_{k in H} x_k y_k - r r',  r = ||x_R||.  Every image row carries
+// r^ >= ||bf16(x)_R|| in its last K-slot (hm_rest_norm_bf16), which all other kernels multiply by a stationary 0.  Here the
+// stationary side keeps +r^ there and only the HEAD k-steps of H in registers, the time step first: after HEAD k-steps the
+// accumulators hold -(a lower bound of the group's u), which is reduced and compared with the bound of finish_group.
+// When no lane is below it the group is done after HEAD of its NP k-steps; otherwise the group is recomputed by the
+// complete chain (k-steps 0 .. NP-1 in order, stationary fragments re-read from the image, fourth slot 0: the operands
+// and the order of the kernel without the test, hence its values bit for bit) and goes through finish_group as ever.
+// Why the same delta (hm_scan_delta) is enough: let U_b be the exact value of the complete form on the bf16 operands and
+// H_b that of the head form; H_b <= U_b by the inequality above, applied to the operands the matrix cores see (the time
+// products are the same three terms in both; r^ r^' is exact in fp32; a flushed subnormal operand only shrinks a rest
+// product, and r^ is never subnormal).  delta's bf16 part bounds |U_b - u_exact|.  Its fp32 part, (kterms + 8) ulps
+// of rmax2, was sized for the roundings of a chain of kterms products whose absolute values sum to <= rmax2 plus those of the
+// canonical value; the head chain has at most 16 * HEAD + 1 <= kterms - 7 products, and their absolute values sum to
+// <= (1 + 2^-6) rmax2 (r^ exceeds ||x_R|| by at most two bf16 roundings): (kterms - 7) * 1.016 <= kterms for kterms <= 437.
+// So head_f <= H_b + (that part) <= u_c + delta: a group whose lanes all have head_f >= bound holds no pair that the
+// complete chain could have reported.  tests/test_scan_head_bound.py checks the inequality in numpy.
+template <int NG, int SIGN, int MODE, int BF, int TM, int WPB, int SUB, bool WK = false, int HEAD = 0>
 __global__ __launch_bounds__(64 * WPB, 2) void hm_scan_kernel(const ScanArgs p)
 {
     static_assert(SUB % 2 == 0, "the two accumulator sets alternate between column groups: an even number per tile");
@@ -104,6 +123,8 @@ __global__ __launch_bounds__(64 * WPB, 2) void hm_scan_kernel(const ScanArgs p)
     constexpr int NTHREADS = 64 * WPB;
     static_assert(TILE_BYTES % 1024 == 0, "tiles are moved in 1 KiB pieces");
     static_assert(DIST * PPW <= 60, "the counted wait must fit vmcnt");
+    static_assert(HEAD == 0 || (BF != 0 && SIGN != 0 && MODE == HM_MODE_ARGMIN && PIPE && HEAD == hm_head_steps(NG)),
+                  "the head test: bf16 form, lorentz sign, argmin, two accumulator sets, the head set the image's r^ was built for");
     extern __shared__ __attribute__((aligned(16))) char smem[];   // NBUF * TILE_LDS (+ hist)
 
     if (p.stop != nullptr && *p.stop != 0u) return;     // a device-resident loop has ended
@@ -150,12 +171,15 @@ __global__ __launch_bounds__(64 * WPB, 2) void hm_scan_kernel(const ScanArgs p)
         if (g0 < gk) gk = g0;
     }
 
+    int hg_tot = 0, hc_tot = 0;          // head test: groups this wave ran / had to recompute (reported at the end, ScanArgs::head_bad)
+
     // ---- stationary A fragments: lane (r, h) keeps its operands of every k-step in registers ----
     float2 a[BF ? 1 : TM][BF ? 1 : NP];            // fp32 form: 2 operands (two k-steps) per group
     uint4 a16[BF ? TM : 1][BF ? NP : 1];           // bf16 form: 8 bf16 per 16-wide k-step
+    uint4 a16t[HEAD ? TM : 1];                     // head test: the time k-step's fragment with +r^' in the fourth time slot
     // bf16 form: the k-step g operand of a lane from its row pointer (row start + 16 * h): 8 K-slots = one 16-byte chunk;
     // the half step of an odd chunk count holds 4 slots per lane (8 bytes at chunk start + 8 * h)
-    auto frag_at = [&](const auto* base, int g) -> uint4 {
+    auto frag_at = [&](const auto* base, int g) __attribute__((always_inline)) -> uint4 {
         const char* q = reinterpret_cast<const char*>(base);
         if (HALF_LAST && g == NP - 1) {
             const uint2 v = *reinterpret_cast<const uint2*>(q + 32 * g - 8 * h);
@@ -163,7 +187,7 @@ __global__ __launch_bounds__(64 * WPB, 2) void hm_scan_kernel(const ScanArgs p)
         }
         return *reinterpret_cast<const uint4*>(q + 32 * g);
     };
-    auto mfma16 = [&](const uint4& av, const uint4& bv, const f32x16& cv, int g) -> f32x16 {
+    auto mfma16 = [&](const uint4& av, const uint4& bv, const f32x16& cv, int g) __attribute__((always_inline)) -> f32x16 {
         if (HALF_LAST && g == NP - 1) {
             typedef short s16x4 __attribute__((ext_vector_type(4)));
             const uint2 a2 = make_uint2(av.x, av.y), b2 = make_uint2(bv.x, bv.y);
@@ -171,7 +195,7 @@ __global__ __launch_bounds__(64 * WPB, 2) void hm_scan_kernel(const ScanArgs p)
         }
         return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, av), __builtin_bit_cast(bf16x8, bv), cv, 0, 0, 0);
     };
-    auto load_a = [&]() {
+    auto load_a = [&]() __attribute__((always_inline)) {
     if constexpr (BF) {
 #pragma unroll
         for (int tm = 0; tm < TM; ++tm) {
@@ -186,6 +210,17 @@ __global__ __launch_bounds__(64 * WPB, 2) void hm_scan_kernel(const ScanArgs p)
                 const uint32_t t0 = (hi16 | (hi16 << 16)) ^ 0x80008000u, t1 = lo16 ^ 0x8000u;
                 if (HALF_LAST) { a16[tm][NP - 1].x = t0; a16[tm][NP - 1].y = t1; }
                 else { a16[tm][NP - 1].z = t0; a16[tm][NP - 1].w = t1; }
+            }
+            if constexpr (HEAD > 0) {
+                // head test: the same fragment with the row's rest norm in the fourth time slot, [-hi, -hi, -lo, +r^'],
+                // r^' = max(r^, smallest normal): a zero r^ must not turn a huge r^ of the partner into 0
+                uint32_t rh = (uint32_t)*reinterpret_cast<const unsigned short*>(p.img16 + (int64_t)(i0w + 32 * tm + r) * RB16 + 16 * NG - 2);
+                rh = rh < 0x0080u ? 0x0080u : rh;
+                a16t[tm] = a16[tm][NP - 1];
+                if (h == 1) {
+                    if (HALF_LAST) a16t[tm].y |= rh << 16;
+                    else a16t[tm].w |= rh << 16;
+                }
             }
         }
     } else {
@@ -202,7 +237,7 @@ __global__ __launch_bounds__(64 * WPB, 2) void hm_scan_kernel(const ScanArgs p)
     // ---- LDS-DMA of one tile: wave w moves the PPW consecutive pieces [w * PPW, (w + 1) * PPW), four per
     // statement, through inline asm so that hipcc neither sees nor drains them; pieces past NPIECE (slot padding)
     // read the first KiB of the next tile: in bounds (the image is allocated with slack rows), unused.
-    auto dma_tile = [&](int ct, int buf) {
+    auto dma_tile = [&](int ct, int buf) __attribute__((always_inline)) {
         const char* src = (BF ? reinterpret_cast<const char*>(p.img16) : reinterpret_cast<const char*>(p.img)) +
                           (int64_t)ct * TILE_BYTES + lane * 16 + wave * (PPW * 1024);
         const uint32_t dst = __builtin_amdgcn_readfirstlane(lds_base + (uint32_t)buf * (uint32_t)TILE_LDS + (uint32_t)wave * (PPW * 1024u));
@@ -220,6 +255,7 @@ __global__ __launch_bounds__(64 * WPB, 2) void hm_scan_kernel(const ScanArgs p)
     constexpr bool DEEP = (BF != 0) && PIPE && (TM <= 2) && HM_SCAN_DEEP_PREFETCH;
     // (the one-set kernels -- 128-row waves -- have no registers left for a second fragment set: 60 spills when tried;
     // requesting all fragments of a group behind its first k-step measured 0.5 % slower than one-ahead requests there)
+    static_assert(HEAD == 0 || DEEP, "the head walk keeps its fragments in bfr[][]: needs the two fragment register sets");
     uint4 bfr[2][DEEP ? NP : 1];
     float2 bpre = make_float2(0.f, 0.f);
 
@@ -230,7 +266,7 @@ __global__ __launch_bounds__(64 * WPB, 2) void hm_scan_kernel(const ScanArgs p)
     // `red_c` = true: the bound test's reduction over the OTHER accumulator set (the group finished before) is
     // folded into the k-steps, a few elements behind each step's MFMAs -- written into the same straight-line code
     // so that the vector ALU work rides in the matrix instructions' issue shadow; its result goes to `ext`.
-    auto mma_group = [&](auto set_c, auto red_c, int buf, int sub, bool fresh, float& ext) {
+    auto mma_group = [&](auto set_c, auto red_c, int buf, int sub, bool fresh, float& ext) __attribute__((always_inline)) {
         constexpr int set = decltype(set_c)::value;
         constexpr bool RED = decltype(red_c)::value;
         constexpr int QN = 16 * TM;
@@ -302,7 +338,7 @@ __global__ __launch_bounds__(64 * WPB, 2) void hm_scan_kernel(const ScanArgs p)
     // of the group are in bfr[set] before its MFMAs start -- requested by the previous group (`fresh` = false) -- and
     // the next group's go out to bfr[set ^ 1] first thing (`prefetch`), so the LDS latency is paid behind fourteen
     // MFMAs instead of in front of every second pair.  The other set's bound-test reduction rides along as in mma_group.
-    auto mma_group_deep = [&](auto set_c, int buf, int sub, bool fresh, bool prefetch, float& ext) {
+    auto mma_group_deep = [&](auto set_c, int buf, int sub, bool fresh, bool prefetch, float& ext) __attribute__((always_inline)) {
         constexpr int set = decltype(set_c)::value;
         constexpr int QN = 16 * TM;
         if constexpr (DEEP) {
@@ -348,7 +384,7 @@ __global__ __launch_bounds__(64 * WPB, 2) void hm_scan_kernel(const ScanArgs p)
     };
 
     // the lane's most promising u of accumulator set `set` (acc = -M: u = acc under the reference sign, -acc under lorentz)
-    auto reduce_group = [&](auto set_c) -> float {
+    auto reduce_group = [&](auto set_c) __attribute__((always_inline)) -> float {
         constexpr int set = decltype(set_c)::value;
         float ext = acc[set][0][0];
 #pragma unroll
@@ -362,7 +398,7 @@ __global__ __launch_bounds__(64 * WPB, 2) void hm_scan_kernel(const ScanArgs p)
     // a time (a rolled loop: the hot loop must not inherit its register pressure).  Per-element predicates are
     // evaluated twice (count, then write); the second evaluation runs on laundered copies of the bounds so that the
     // compiler does not keep the predicates alive across the wave scan.
-    auto finish_group = [&](auto set_c, float ext_u, int j0s) {
+    auto finish_group = [&](auto set_c, float ext_u, int j0s) __attribute__((always_inline)) {
         constexpr int set = decltype(set_c)::value;
         float bound_f = pre_f;
         uint32_t best_bits = 0xffffffffu, best_low = 0xffffffffu;
@@ -487,6 +523,106 @@ __global__ __launch_bounds__(64 * WPB, 2) void hm_scan_kernel(const ScanArgs p)
         }
     };
 
+    // ---- the head test (HEAD > 0; see the kernel's header) ----
+    // the HEAD k-steps of column group `sub` into acc[set], software-pipelined like mma_group_deep: the fragments are in
+    // bfr[set] before the MFMAs start (requested by the previous group unless `fresh`), the next group's go out to
+    // bfr[set ^ 1] behind the first k-step, and with RED the reduction of the other set -- the head values of the group
+    // before -- rides in the issue shadow of the MFMAs; its result goes to `ext`
+    auto head_group = [&](auto set_c, auto red_c, int buf, int sub, bool fresh, float& ext) __attribute__((always_inline)) {
+        constexpr int set = decltype(set_c)::value;
+        constexpr bool RED = decltype(red_c)::value;
+        constexpr int QN = 16 * TM;
+        if constexpr (HEAD > 0) {
+            const char* bt = smem + buf * TILE_LDS + (sub * 32 + r) * RB16 + 16 * h;
+            if (fresh) {
+#pragma unroll
+                for (int k = 0; k < HEAD; ++k) bfr[set][k] = frag_at(bt, hm_head_kstep(k, NP));
+            }
+            if constexpr (RED) ext = acc[set ^ 1][0][0];
+            auto kstep = [&](auto k_c) {                 // (k as a type: every register array index below is a constant)
+                constexpr int k = decltype(k_c)::value;
+                constexpr int g = hm_head_kstep(k, NP);
+#pragma unroll
+                for (int tm = 0; tm < TM; ++tm) {
+                    if constexpr (k == 0) {
+                        f32x16 z;
+#pragma unroll
+                        for (int e = 0; e < 16; ++e) z[e] = 0.0f;
+                        acc[set][tm] = mfma16(a16t[tm], bfr[set][k], z, g);
+                    } else {
+                        acc[set][tm] = mfma16(a16[tm][g], bfr[set][k], acc[set][tm], g);
+                    }
+                }
+                if constexpr (RED) {
+#pragma unroll
+                    for (int q = (k * QN) / HEAD; q < ((k + 1) * QN) / HEAD; ++q)
+                        ext = __builtin_fmaxf(ext, acc[set ^ 1][q / 16][q % 16]);
+                }
+            };
+            kstep(std::integral_constant<int, 0>{});
+            __builtin_amdgcn_sched_barrier(0);
+            // unconditional, like mma_group_deep's: behind the last group of a tile the addresses fall into the next slot or
+            // the slack behind the ring and the data is never used
+#pragma unroll
+            for (int k = 0; k < HEAD; ++k) bfr[set ^ 1][k] = frag_at(bt + 32 * RB16, hm_head_kstep(k, NP));
+            __builtin_amdgcn_sched_barrier(0);
+            static_assert(HEAD <= 4, "the head k-steps are written out");
+            if constexpr (HEAD > 1) kstep(std::integral_constant<int, 1>{});
+            if constexpr (HEAD > 2) kstep(std::integral_constant<int, 2>{});
+            if constexpr (HEAD > 3) kstep(std::integral_constant<int, 3>{});
+            if constexpr (RED) ext = -ext;
+        }
+    };
+    // bound test of a group's head values (`ext_u`: the smallest lower bound of u among the lane's elements of acc[set]); a
+    // group that fails it is recomputed by the complete chain -- a rolled loop that reads the stationary fragments from
+    // the image again (L2), so the hot loop inherits no registers from it -- and handed to finish_group.  The group's
+    // columns must still be in ring slot `buf`: the head walk tests the last group of a tile before the tile's barrier.
+    auto head_finish = [&](auto set_c, float ext_u, int buf, int sub, int j0s) __attribute__((always_inline)) -> bool {
+        constexpr int set = decltype(set_c)::value;
+        if constexpr (HEAD > 0) {
+            float bound_f = pre_f;                       // (the ARGMIN bound of finish_group)
+            const uint32_t best_bits = (uint32_t)(gk >> 32);
+            if (best_bits != 0xffffffffu) {
+                const float bb = hm::bitsf(best_bits + hm_tie_slack(best_bits)) + 2.0f * delta;
+                if (bb < bound_f) bound_f = bb;
+            }
+            if (__ballot(ext_u < bound_f) == 0ull) return false;
+            const char* bt = smem + buf * TILE_LDS + (sub * 32 + r) * RB16 + 16 * h;
+            const unsigned char* as = p.img16 + (int64_t)(i0w + r) * RB16 + 16 * h;
+#pragma unroll
+            for (int tm = 0; tm < TM; ++tm)
+#pragma unroll
+                for (int e = 0; e < 16; ++e) acc[set][tm][e] = 0.0f;
+#pragma unroll 1
+            for (int g = 0; g < NP - 1; ++g) {
+                const uint4 bv = *reinterpret_cast<const uint4*>(bt + 32 * g);
+#pragma unroll
+                for (int tm = 0; tm < TM; ++tm) {
+                    const uint4 av = *reinterpret_cast<const uint4*>(as + (int64_t)(32 * tm) * RB16 + 32 * g);
+                    acc[set][tm] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, av), __builtin_bit_cast(bf16x8, bv), acc[set][tm], 0, 0, 0);
+                }
+            }
+            {
+                const uint4 bv = frag_at(bt, NP - 1);
+#pragma unroll
+                for (int tm = 0; tm < TM; ++tm) {
+                    uint4 av = frag_at(as + (int64_t)(32 * tm) * RB16, NP - 1);
+                    if (h == 1) {                        // [hi, lo, hi, r^] -> [-hi, -hi, -lo, 0], as load_a of the kernels without the test
+                        const uint32_t z = HALF_LAST ? av.x : av.z;
+                        const uint32_t hi16 = z & 0xffffu, lo16 = z >> 16;
+                        const uint32_t t0 = (hi16 | (hi16 << 16)) ^ 0x80008000u, t1 = lo16 ^ 0x8000u;
+                        if (HALF_LAST) { av.x = t0; av.y = t1; }
+                        else { av.z = t0; av.w = t1; }
+                    }
+                    acc[set][tm] = mfma16(av, bv, acc[set][tm], NP - 1);
+                }
+            }
+            finish_group(set_c, reduce_group(set_c), j0s);
+            return true;
+        }
+        return false;
+    };
+
     // ---- work distribution: block b owns item b of the host's list (hm_prepare_scan); with the item queue (p.dyn) the grid
     // is the resident set and every block goes on drawing items of the same list, in order, from the queue word p.q_ctr ----
     constexpr int QOFF = NBUF * TILE_LDS + 32 * ROW_BYTES + (MODE == HM_MODE_HIST ? (int)sizeof(uint32_t) * HM_HIST_BINS : 0);
@@ -563,7 +699,51 @@ __global__ __launch_bounds__(64 * WPB, 2) void hm_scan_kernel(const ScanArgs p)
             asm volatile("global_atomic_add_x2 %0, %1, %2, off sc0" : "=v"(q_raw) : "v"(p.q_ctr), "v"(1ull) : "memory");
         dma_tile(ct_next, buf_next);
 
-        if constexpr (!PIPE) {
+        constexpr bool head_tile = HEAD > 0;     // a head kernel walks every tile this way
+        if constexpr (HEAD > 0) {
+          {
+            // head walk: the groups of the tile alternate between the accumulator sets; group g's head k-steps carry the
+            // reduction of group g - 1's head values, whose test follows.  Nothing is pending across the tile's barrier (the
+            // recomputation of a failed group reads its columns from this ring slot): the last group is reduced on its own.
+            bool hp = false;
+            int hg = 0, hc = 0;          // groups of this tile that ran / that had to be recomputed
+#pragma unroll 1
+            for (int sp = 0; sp < SUB / 2; ++sp) {
+                {
+                    const int sub = 2 * sp;
+                    const int j0s = j0 + sub * 32;
+                    const bool do_c = wave_active && (j0s + 31 > i0w);
+                    float ext_u = 0.0f;
+                    if (do_c && hp) {
+                        head_group(std::integral_constant<int, 0>{}, std::true_type{}, buf, sub, false, ext_u);
+                    } else {
+                        if (do_c) head_group(std::integral_constant<int, 0>{}, std::false_type{}, buf, sub, true, ext_u);
+                        if (hp) ext_u = reduce_group(std::integral_constant<int, 1>{});
+                    }
+                    if (hp) { ++hg; hc += head_finish(std::integral_constant<int, 1>{}, ext_u, buf, sub - 1, j0s - 32) ? 1 : 0; }
+                    hp = do_c;
+                }
+                {
+                    const int sub = 2 * sp + 1;
+                    const int j0s = j0 + sub * 32;
+                    const bool do_c = wave_active && (j0s + 31 > i0w);
+                    float ext_u = 0.0f;
+                    if (do_c && hp) {
+                        head_group(std::integral_constant<int, 1>{}, std::true_type{}, buf, sub, false, ext_u);
+                    } else {
+                        if (do_c) head_group(std::integral_constant<int, 1>{}, std::false_type{}, buf, sub, true, ext_u);
+                        if (hp) ext_u = reduce_group(std::integral_constant<int, 0>{});
+                    }
+                    if (hp) { ++hg; hc += head_finish(std::integral_constant<int, 0>{}, ext_u, buf, sub - 1, j0s - 32) ? 1 : 0; }
+                    hp = do_c;
+                }
+            }
+            if (hp) { ++hg; hc += head_finish(std::integral_constant<int, 1>{}, reduce_group(std::integral_constant<int, 1>{}), buf, SUB - 1, j0 + (SUB - 1) * 32) ? 1 : 0; }
+            hg_tot += hg; hc_tot += hc;
+          }
+        }
+        if constexpr (head_tile) {
+        } else if constexpr (!PIPE) {
             // one accumulator set: MFMAs, then the bound test of the same group (the other resident block of the CU
             // fills the matrix pipe meanwhile); the first fragment of the next group is still requested early
             bool prev = false;
@@ -672,6 +852,10 @@ __global__ __launch_bounds__(64 * WPB, 2) void hm_scan_kernel(const ScanArgs p)
     }
     }   // items
 
+    if constexpr (HEAD > 0) {
+        // a wave that had to recompute most of its groups tells the host that the bound is too loose for this kernel
+        if (lane == 0 && hg_tot >= 16 && 2 * hc_tot > hg_tot) __hip_atomic_store(p.head_bad, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    }
     if (MODE == HM_MODE_TOPK) {
         // one 64-bit atomic per wave for the sure count
         unsigned long long s = sure_total;
@@ -689,7 +873,7 @@ __global__ __launch_bounds__(64 * WPB, 2) void hm_scan_kernel(const ScanArgs p)
 // ------------------------------------------------------------------------------------------------
 // launch
 // ------------------------------------------------------------------------------------------------
-template <int NG, int SIGN, int MODE, int BF, int TM, int WPB, int SUB, bool WK = false>
+template <int NG, int SIGN, int MODE, int BF, int TM, int WPB, int SUB, bool WK = false, int HEAD = 0>
 static hipError_t hm_launch_scan_t(hm_engine* e, const ScanArgs& a, dim3 grid, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1)
 {
     const size_t row_bytes = BF ? 16 * hm_row16_chunks(NG) : 4 * hm_row_floats(NG);
@@ -699,7 +883,7 @@ static hipError_t hm_launch_scan_t(hm_engine* e, const ScanArgs& a, dim3 grid, h
     lds += (size_t)32 * row_bytes;                                          // slack behind the ring: the early request of "the next group's" fragment
     if (MODE == HM_MODE_HIST) lds += sizeof(uint32_t) * HM_HIST_BINS;      // (HIST mode keeps its bins there; they are only read by that request)
     lds += 16;                                                              // the item queue's broadcast word
-    const void* fn = reinterpret_cast<const void*>(&hm_scan_kernel<NG, SIGN, MODE, BF, TM, WPB, SUB, WK>);
+    const void* fn = reinterpret_cast<const void*>(&hm_scan_kernel<NG, SIGN, MODE, BF, TM, WPB, SUB, WK, HEAD>);
     if (lds > 48 * 1024 && e->attr_done.find(fn) == e->attr_done.end()) {     // per engine (= per device), not process-wide
         hipError_t st = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (st != hipSuccess) return st;
@@ -728,8 +912,8 @@ static hipError_t hm_launch_scan_t(hm_engine* e, const ScanArgs& a, dim3 grid, h
             b.q_ctr = e->d_queue + 16 * ((b.ctr64 == e->d_ctr64) ? 0 : 1);      // one word per counter set (the pipelined loop alternates them)
         }
     }
-    if (ev0 != nullptr || ev1 != nullptr) hipExtLaunchKernelGGL((hm_scan_kernel<NG, SIGN, MODE, BF, TM, WPB, SUB, WK>), grid, dim3(64 * WPB), lds, s, ev0, ev1, 0, b);
-    else hipLaunchKernelGGL((hm_scan_kernel<NG, SIGN, MODE, BF, TM, WPB, SUB, WK>), grid, dim3(64 * WPB), lds, s, b);
+    if (ev0 != nullptr || ev1 != nullptr) hipExtLaunchKernelGGL((hm_scan_kernel<NG, SIGN, MODE, BF, TM, WPB, SUB, WK, HEAD>), grid, dim3(64 * WPB), lds, s, ev0, ev1, 0, b);
+    else hipLaunchKernelGGL((hm_scan_kernel<NG, SIGN, MODE, BF, TM, WPB, SUB, WK, HEAD>), grid, dim3(64 * WPB), lds, s, b);
     return hipGetLastError();
 }
 
@@ -740,6 +924,15 @@ static hipError_t hm_launch_scan_ng(hm_engine* e, int sign, int mode, const Scan
     if (sign) {
         if (mode == HM_MODE_TOPK) return hm_launch_scan_t<NG, 1, HM_MODE_TOPK, BF, TM, WPB, SUB>(e, a, grid, s, ev0, ev1);
         if (mode == HM_MODE_ARGMIN) {
+            // the head test (knob `head`, 0 = off; hm_head_live: only when the host expects a tight bound): 64-row waves of
+            // the bf16 form whose rows have more k-steps than the head.  Otherwise the unchanged HEAD = 0 kernel.
+            constexpr int HD = (BF != 0 && TM <= HM_SCAN_PIPE_MAX_TM) ? hm_head_steps(NG) : 0;
+            if constexpr (HD > 0) {
+                if (hm_head_live(e)) {
+                    if (a.key_wide) return hm_launch_scan_t<NG, 1, HM_MODE_ARGMIN, BF, TM, WPB, SUB, true, HD>(e, a, grid, s, ev0, ev1);
+                    return hm_launch_scan_t<NG, 1, HM_MODE_ARGMIN, BF, TM, WPB, SUB, false, HD>(e, a, grid, s, ev0, ev1);
+                }
+            }
             if (a.key_wide) return hm_launch_scan_t<NG, 1, HM_MODE_ARGMIN, BF, TM, WPB, SUB, true>(e, a, grid, s, ev0, ev1);
             return hm_launch_scan_t<NG, 1, HM_MODE_ARGMIN, BF, TM, WPB, SUB>(e, a, grid, s, ev0, ev1);
         }
@@ -863,6 +1056,7 @@ bool hm_prepare_scan(hm_engine* e, const Bounds& b, int64_t row_begin, int64_t r
     a.hist = e->d_hist;
     a.sample_stride = 1;
     a.rmax2_bits = e->d_rmax2;
+    a.head_bad = &e->h->head_bad;
     a.stop = nullptr;
     a.key_wide = e->key_ib > HM_KEY_IB_NARROW ? 1 : 0;
     a.key_si = 32 - e->key_ib;
