@@ -58,6 +58,7 @@ EXPORTED_SYMBOLS = (
     "hm_edge_loss_fwd", "hm_edge_loss_bwd", "hm_debug_edge_loss_form", "hm_negsample_create", "hm_negsample_destroy", "hm_negsample_check_csr",
     "hm_negsample_set_csr", "hm_negsample_sample",
     "hm_centroid_fwd", "hm_centroid_bwd", "hm_debug_centroid_form",
+    "hm_recon_slots", "hm_recon_counts", "hm_debug_recon_layout",
 )
 
 
@@ -204,6 +205,9 @@ def load() -> C.CDLL:
     L.hm_centroid_fwd.argtypes = [vp, i64, i64, C.c_int, vp, i64, vp, vp, vp, i64, vp, vp, vp]
     L.hm_centroid_bwd.argtypes = [vp, i64, i64, C.c_int, vp, i64, vp, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp]
     L.hm_debug_centroid_form.argtypes = [C.c_int]
+    L.hm_recon_slots.argtypes = [vp, vp, i64, i64, vp, i64, vp, i64, vp, vp, vp, vp]
+    L.hm_recon_counts.argtypes = [vp, i64, i64, C.c_int, vp, vp, vp, vp, i64, i64, vp, vp, vp, vp, vp, vp]
+    L.hm_debug_recon_layout.argtypes = [C.c_int]
     L.hm_negsample_create.argtypes = [C.POINTER(vp), C.c_int]
     L.hm_negsample_destroy.argtypes = [vp]
     L.hm_negsample_check_csr.argtypes = [vp, vp, i64]

@@ -6,7 +6,8 @@ optimiser, all on the HIP device) from the command line.
 line, two node names separated by a tab; node indices are then the order of first appearance.  Writes ``embeddings.pt`` (fp32
 ``[V, dim + 1]``), ``nodes.json`` (node names in row order) and ``train_log.json`` (hyper-parameters and the mean loss of every
 epoch) to ``--output-dir``; with ``--eval-pairs N > 0`` also ``distortion_stats.json`` from ``compute_distortion`` over N
-sampled pairs.  The reference has no counterpart: it never trains its embeddings.
+sampled pairs; with ``--eval-reconstruction`` also ``reconstruction_stats.json``: ``reconstruction_metrics`` (mean rank and mAP
+of the graph's edges) of the trained table and, under ``"initial"``, of the table training started from.  The reference has no counterpart: it never trains its embeddings.
 """
 from __future__ import annotations
 
@@ -18,7 +19,8 @@ from typing import Dict, List, Tuple
 import torch
 import typer
 
-from hyptokenizer_amd.embedding.graph_embedding import GraphEmbeddingResult, fit_graph_embedding
+from hyptokenizer_amd.embedding.graph_embedding import GraphEmbeddingResult, fit_graph_embedding, init_table
+from hyptokenizer_amd.embedding.graph_metrics import reconstruction_metrics
 from hyptokenizer_amd.scripts.eval_hierarchy import compute_distortion, load_wordnet_graph, set_seeds
 
 logging.basicConfig(level=logging.INFO, format="%(asctime)s - %(name)s - %(levelname)s - %(message)s")
@@ -66,7 +68,7 @@ def load_graph(graph_path: str):
 def train_graph_embeddings(graph_path: str, output_dir: str, dim: int = 10, epochs: int = 50, batch_size: int = 1024,
                            num_negatives: int = 50, lr: float = 0.3, burn_in_epochs: int = 10, burn_in_factor: float = 0.1,
                            optimizer: str = "rsgd", init_scale: float = 1e-3, seed: int = 0, curvature: float = 1.0,
-                           eval_pairs: int = 0, log_every: int = 1) -> GraphEmbeddingResult:
+                           eval_pairs: int = 0, log_every: int = 1, eval_reconstruction: bool = False) -> GraphEmbeddingResult:
     graph = load_graph(graph_path)
     params = dict(dim=dim, epochs=epochs, batch_size=batch_size, num_negatives=num_negatives, lr=lr, burn_in_epochs=burn_in_epochs,
                   burn_in_factor=burn_in_factor, optimizer=optimizer, init_scale=init_scale, seed=seed, c=curvature)
@@ -84,6 +86,13 @@ def train_graph_embeddings(graph_path: str, output_dir: str, dim: int = 10, epoc
                                       device=result.table.device, sign_convention="lorentz")
         with open(os.path.join(output_dir, "distortion_stats.json"), "w") as f:
             json.dump(stats, f, indent=4)
+    if eval_reconstruction:
+        table0 = init_table(len(result.node_names), dim, init_scale, seed, result.table.device)
+        stats = reconstruction_metrics(result.table, graph, node_mapping=result.node_mapping)
+        stats["initial"] = reconstruction_metrics(table0, graph, node_mapping=result.node_mapping)
+        with open(os.path.join(output_dir, "reconstruction_stats.json"), "w") as f:
+            json.dump(stats, f, indent=4)
+        logger.info(f"Reconstruction: mean rank {stats['mean_rank']:.3f}, mAP {stats['map']:.4f} over {stats['num_pairs']} pairs")
     return result
 
 
@@ -102,11 +111,13 @@ def main(
     seed: int = 0,
     curvature: float = 1.0,
     eval_pairs: int = 0,
+    eval_reconstruction: bool = False,
 ) -> None:
     """Train hyperbolic embeddings of a graph."""
     train_graph_embeddings(graph_path=graph_path, output_dir=output_dir, dim=dim, epochs=epochs, batch_size=batch_size,
                            num_negatives=num_negatives, lr=lr, burn_in_epochs=burn_in_epochs, burn_in_factor=burn_in_factor,
-                           optimizer=optimizer, init_scale=init_scale, seed=seed, curvature=curvature, eval_pairs=eval_pairs)
+                           optimizer=optimizer, init_scale=init_scale, seed=seed, curvature=curvature, eval_pairs=eval_pairs,
+                           eval_reconstruction=eval_reconstruction)
 
 
 if __name__ == "__main__":

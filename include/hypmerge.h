@@ -711,6 +711,45 @@ int hm_negsample_set_csr(hm_negsample* g, const int64_t* row_ptr, const int32_t*
 int hm_negsample_sample(hm_negsample* g, const int64_t* pairs_dev, int64_t n_pairs, int64_t k, uint64_t seed, int64_t step,
                         int max_tries, int64_t* out_dev, void* stream);
 
+/* Graph reconstruction: where the graph neighbours of a node land when every other node is ranked by its
+ * distance to it, as integer counts, without a [nodes, V] distance slab.  x_dev is fp32 [V, d1] with leading dimension ld;
+ * D[u, v] is the canonical fp32 distance at c = 1 under the "lorentz" sign (the bits of hm_batch_distance).  The calls take no
+ * curvature: a division by sqrt(c) could merge distinct fp32 distances into ties.  The graph is a CSR without self-loops whose
+ * rows are sorted and free of repeats (what hm_negsample_check_csr accepts), symmetric or not.  A slot is a directed edge
+ * e = (u, o), o in N(u); slots with the same anchor are contiguous and form a segment.  Per slot, int32:
+ *   less_all[e]  = #{ v != u    : D[u, v] <  D[u, o] }
+ *   equal_all[e] = #{ v != u    : D[u, v] == D[u, o] }      (>= 1: v = o)
+ *   less_nb[e]   = #{ v in N(u) : D[u, v] <  D[u, o] }
+ *   equal_nb[e]  = #{ v in N(u) : D[u, v] == D[u, o] }      (>= 1)
+ * NaN orders as in hm_retrieval_ranks: greater than every number, equal to NaN; a NaN pivot has less = the number of
+ * distances that are numbers and equal = the number of NaN ones.  From the counts
+ *   rank[e]      = 1 + less_all[e] - less_nb[e]             (position among the non-neighbours, ties optimistic)
+ *   precision[e] = (less_nb[e] + equal_nb[e]) / (less_all[e] + equal_all[e])
+ *   mean rank    = sum_e rank[e] / #slots;   AP(u) = mean of precision over the slots of u;   mAP = mean of AP(u), deg(u) > 0.
+ * hm_recon_slots lists the slots of n_seg anchors in CSR order: nodes_dev int64 [n_seg] (NULL: node g is anchor g, n_seg = V),
+ * seg_ptr_dev int64 [n_seg + 1] the running sum of their degrees from 0, n_slots = seg_ptr[n_seg]; it writes slot_anchor,
+ * slot_pivot and slot_seg (the position of the slot's anchor in nodes), int32 [n_slots] each.
+ * hm_recon_counts takes such slots (any list of contiguous segments will do: slot e belongs to segment slot_seg[e], which
+ * spans the slots seg_ptr[g] .. seg_ptr[g + 1] - 1) and writes the four vectors; u_scratch_dev fp32 [n_slots] is its only
+ * working memory (the clamped argument of acosh of every slot's pivot).  A slot whose anchor or pivot lies outside [0, V), or
+ * whose segment outside [0, n_seg), is never dereferenced and gets -1 in all four vectors; the neighbour counts of the other
+ * slots of its segment are then unspecified.  Every element is written once, no atomics: two calls give the same bits.
+ * Engine-independent; errors through hm_last_error(NULL); asynchronous on `stream`.  HM_E_ARG before the device is touched for
+ * a NULL pointer (with n_slots == 0 only x_dev / row_ptr_dev and seg_ptr_dev are required), d1 outside 2..129, ld < d1,
+ * V outside 1..2^31 - 1, negative (or >= 2^31) nnz, n_seg, n_slots, slots without a segment.  n_slots == 0 launches nothing.
+ * Replaces: nothing the reference runs (it never evaluates an embedding against its graph). */
+int hm_recon_slots(const int64_t* row_ptr_dev, const int32_t* col_dev, int64_t V, int64_t nnz, const int64_t* nodes_dev,
+                   int64_t n_seg, const int64_t* seg_ptr_dev, int64_t n_slots, int32_t* slot_anchor_dev, int32_t* slot_pivot_dev,
+                   int32_t* slot_seg_dev, void* stream);
+int hm_recon_counts(const float* x_dev, int64_t ld, int64_t V, int d1, const int32_t* slot_anchor_dev, const int32_t* slot_pivot_dev,
+                    const int32_t* slot_seg_dev, const int64_t* seg_ptr_dev, int64_t n_slots, int64_t n_seg, int32_t* less_all_dev,
+                    int32_t* equal_all_dev, int32_t* less_nb_dev, int32_t* equal_nb_dev, float* u_scratch_dev, void* stream);
+/* Test / tuning hook (results never depend on it): the tile layout of hm_recon_counts' walk from now on, process-wide.
+ * 0 = the default (chosen by width from measurements: layout 1 for d1 < 97, layout 2 from there on), 1 = anchor
+ * and partner rows in LDS, 2 = anchor rows in registers and partner rows read as 16-byte LDS broadcasts (d1 >= 9; narrower
+ * rows always take layout 1). */
+int hm_debug_recon_layout(int layout);
+
 /* Test hook: pretend the previous refresh ended on this emission cut (bits of u'); the next whole-table top-k
  * search starts from it as given and has to notice by itself when it is too tight. */
 int hm_debug_force_cut(hm_engine* e, uint32_t cut_bits, int64_t k, float c);
