@@ -146,38 +146,26 @@ extern "C" int hm_shard_merge_steps(hm_engine* e, float c, float thr, float* X_d
     hipStream_t s = (hipStream_t)stream;
     int rc = hm_shard_loop_begin(e, stream);
     if (rc) return rc;
-    const bool time_all = e->time_loops && !e->loop_evs.empty();
-    if (time_all) hm_read_loop_events(e);
-    int64_t all_pairs[HM_LOOP_MAX_STEPS];
-    const int64_t n0 = e->n;
+    HmBatchGuard guard(e);
+    e->tm.begin_segment();
     for (int64_t k = 0; k < steps && rc == HM_OK; ++k) {
         int64_t r0 = 0, r1 = 0;
         hm_partition_rows(e->n, e->world, e->rank, &r0, &r1);
-        if (time_all) {
-            if (k == 0) (void)hipEventRecord(e->loop_evs[2 * HM_LOOP_MAX_STEPS], s);
-            e->step_ev0 = e->loop_evs[2 * k]; e->step_ev1 = e->loop_evs[2 * k + 1];
-            all_pairs[k] = hm_pairs_in_range(e->n, r0, std::min<int64_t>(r1, e->n - 1));
-        }
+        (void)e->tm.open_step(k, hm_pairs_in_range(e->n, r0, std::min<int64_t>(r1, e->n - 1)), s);
         rc = hm_pairwise_argmin_dev(e, c, thr, r0, r1, reinterpret_cast<uint32_t*>(e->d_shard_rec), stream);
-        e->step_ev0 = e->step_ev1 = nullptr;
+        e->tm.close_step();
         if (rc) break;
         ArgminRec* recs = e->d_shard_recs + (size_t)k * e->world;
         const ncclResult_t st = R->AllGather(e->d_shard_rec, recs, 4, ncclInt32, reinterpret_cast<ncclComm_t>(e->comm), s);
         if (st != ncclSuccess) { rc = hm_fail(e, HM_E_COMM, std::string("ncclAllGather: ") + R->GetErrorString(st)); break; }
         rc = hm_shard_merge_step(e, reinterpret_cast<const uint32_t*>(recs), e->world, c, X_dev, ld, k, stream);
     }
-    if (time_all && rc == HM_OK) (void)hipEventRecord(e->loop_evs[2 * HM_LOOP_MAX_STEPS + 1], s);
+    if (rc == HM_OK) (void)e->tm.end_segment(s);
     const int rc_end = hm_shard_loop_end(e, rc == HM_OK ? steps : 0, rec_out, done, stream);
-    if (rc) { e->n = n0; return rc; }
+    if (rc) return rc;
     if (rc_end) return rc_end;
-    if (time_all) {
-        e->last_batch_ms = e->last_batch_scan_ms = 0.f;
-        e->last_batch_steps = 0;
-        if (*done == steps) {
-            e->loop_unread_steps = steps;
-            e->loop_unread_pairs.assign(all_pairs, all_pairs + steps);
-        }
-    }
+    guard.commit();
+    e->tm.commit_segment(steps, *done == steps);
     return HM_OK;
 }
 

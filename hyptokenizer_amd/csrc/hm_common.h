@@ -2,6 +2,8 @@
 //
 //   hm_engine.hip   engine lifetime, table upload, statistics            (host)
 //   hm_state.h      the search state carried from call to call and its named transitions (host)
+//   hm_timing.h     scan timing and statistics, one owner (host)
+//   hm_batch_plan.h the standard loop's redo policy: which steps are issued next, in which form (host, no HIP)
 //   hm_scan.hip     the pair-scan kernel (MFMA prefilter) and its launch  (hot kernel)
 //   hm_search.hip   exact re-evaluation / selection kernels and the search entry points of the ABI
 //   hm_rows.hip     the engine's row work: image construction, merge / midpoint, one-row-vs-all and gathered distances
@@ -106,6 +108,8 @@ __host__ __device__ constexpr int hm_key_ib(int64_t max_rows)
     return ib;
 }
 __host__ __device__ __forceinline__ uint32_t hm_key_low(uint32_t i, uint32_t j, int si, int sj) { return (i << si) | (j >> sj); }
+
+#include "hm_timing.h"
 
 struct ScanArgs {
     const float* img;
@@ -252,13 +256,13 @@ struct hm_engine {
     LoopState* h_loop = nullptr;                // pinned host image of a LoopState: the incremental loop's initial state goes up, and its final state comes back, in ONE copy each
     bool force_f32 = false;                     // set for the length of one retry (HmScopedSet)
     SearchState st;                             // arming, cut prediction, previous list, route memories, pending refresh (hm_state.h)
+    ScanTiming tm;                              // timing events, last-search and loop statistics, totals (hm_timing.h)
     ArgminSeed* d_seed = nullptr;
     ArgminPart* d_parts = nullptr;
     uint32_t* d_hist = nullptr;
     HostCtl* h = nullptr;                  // pinned
     uint4* h_sorted = nullptr;             // pinned
     uint32_t sorted_cap = 0;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
     // software-pipelined standard loop: a second (high-priority) stream for the step's tail work, which then runs under
     // the NEXT step's scan; per buffer set an event behind the scan and one behind the tail; the new row's key per set
     bool pipeline = true;
@@ -288,24 +292,6 @@ struct hm_engine {
     ArgminRec* d_shard_rec = nullptr;      // this rank's record of a step
     ArgminRec* d_shard_recs = nullptr;     // gathered records: HM_LOOP_MAX_STEPS x world
     uint4* d_gather = nullptr;             // refresh: this rank's packed list [k + 1], then the gathered lists [world][k + 1]
-    hipEvent_t step_ev0 = nullptr, step_ev1 = nullptr;   // set around hm_pairwise_argmin_dev by the in-library sharded loop's timing mode
-    // hm_debug_time_loops: an event pair around EVERY scan of a device-resident batch and around the batch itself
-    bool time_loops = false;
-    std::vector<hipEvent_t> loop_evs;     // 2 * HM_LOOP_MAX_STEPS + 2, created on first use
-    float last_batch_ms = 0.f, last_batch_scan_ms = 0.f;
-    int64_t last_batch_steps = 0;
-    // the event pairs of the last complete batch are read when somebody asks (hm_scan_totals, hm_last_loop_timing) or
-    // when the next batch needs the events -- not inside the call a benchmark is timing
-    int64_t loop_unread_steps = 0;
-    std::vector<int64_t> loop_unread_pairs;
-    // stats
-    float last_scan_ms = 0.f;
-    int64_t last_pairs = 0, last_emitted = 0;
-    int last_passes = 0;
-    bool pending_timing = false;
-    int64_t pending_pairs = 0;
-    double tot_scan_ms = 0.0;
-    int64_t tot_pairs = 0, tot_launches = 0;
     std::set<const void*> attr_done;      // kernels whose dynamic-LDS attribute is set on this engine's device
     std::string err;
 };
@@ -331,11 +317,7 @@ inline bool hm_head_live(const hm_engine* e)
     return e->head_force || (e->head_merges >= 3 && e->h != nullptr && e->h->head_bad == 0u);
 }
 inline void hm_head_reset(hm_engine* e) { e->head_merges = 0; if (e->h) e->h->head_bad = 0u; }
-// statistics of one search (hm_last_scan_stats): begin takes in a pending device-side timing and zeroes them; add reads the
-// engine's event pair (ev0, ev1) behind a synchronised scan of `pairs` pairs
-void hm_scan_stats_begin(hm_engine* e);
-void hm_scan_stats_add(hm_engine* e, int64_t pairs, int64_t emitted);
-// an override that lasts for one scope (force_f32 and pipeline around a retry): no return path leaves it switched on
+// an override that lasts for one scope (force_f32 around a retry): no return path leaves it switched on
 template <class T>
 struct HmScopedSet {
     T& ref;
@@ -344,6 +326,21 @@ struct HmScopedSet {
     ~HmScopedSet() { ref = old; }
     HmScopedSet(const HmScopedSet&) = delete;
     HmScopedSet& operator=(const HmScopedSet&) = delete;
+};
+// The loops advance n and head_merges while they enqueue steps the host has not seen merge.  Whatever leaves the scope
+// without commit() -- every error return -- puts both back to the last confirmed values and disarms the search state; the
+// only code that undoes the optimistic advance.
+struct HmBatchGuard {
+    hm_engine* const e;
+    int64_t n, head_merges;
+    bool committed = false;
+    explicit HmBatchGuard(hm_engine* eng) : e(eng), n(eng->n), head_merges(eng->head_merges) {}
+    // the host has read the records of `merged` more merges: the engine's counts are exactly the confirmed ones again
+    void confirm(int64_t merged) { n += merged; head_merges += merged; e->n = n; e->head_merges = head_merges; }
+    void commit() { committed = true; }
+    ~HmBatchGuard() { if (!committed) { e->n = n; e->head_merges = head_merges; e->st.disarm(); } }
+    HmBatchGuard(const HmBatchGuard&) = delete;
+    HmBatchGuard& operator=(const HmBatchGuard&) = delete;
 };
 // hm_graph.hip: default knobs of the graph component.  HM_OK: taken; HM_E_ARG: bad value; 1: not one of its knobs
 int hm_graph_default_knob(const char* name, double value, int clear);
@@ -373,8 +370,6 @@ bool hm_prepare_scan(hm_engine* e, const Bounds& b, int64_t row_begin, int64_t r
 hipError_t hm_launch_scan(hm_engine* e, int mode, const ScanArgs& a, dim3 grid, hipStream_t s, hipEvent_t ev0 = nullptr,
                           hipEvent_t ev1 = nullptr);
 int64_t hm_pairs_in_range(int64_t n, int64_t r0, int64_t r1);
-void hm_flush_pending_timing(hm_engine* e);
-void hm_read_loop_events(hm_engine* e);
 
 // ---- hm_rows.hip ----
 int hm_build_rows(hm_engine* e, const float* X, int64_t ld, int64_t r0, int64_t r1, hipStream_t s);

@@ -148,9 +148,7 @@ static int hm_engine_alloc(hm_engine* e)
     HM_HIP(hipHostMalloc(&e->h, sizeof(HostCtl), hipHostMallocDefault));
     memset(e->h, 0, sizeof(HostCtl));
     HM_HIP(hipHostMalloc(&e->h_sorted, sizeof(uint4) * (size_t)e->sorted_cap, hipHostMallocDefault));
-    // timing events without the system-scope fence a default event adds around the scan
-    HM_HIP(hipEventCreateWithFlags(&e->ev0, hipEventDisableSystemFence));
-    HM_HIP(hipEventCreateWithFlags(&e->ev1, hipEventDisableSystemFence));
+    HM_HIP(e->tm.create());
     return HM_OK;
 }
 
@@ -239,9 +237,7 @@ extern "C" int hm_engine_destroy(hm_engine* e)
     }
     if (e->ev_join) (void)hipEventDestroy(e->ev_join);
     if (e->aux) (void)hipStreamDestroy(e->aux);
-    for (hipEvent_t ev : e->loop_evs) (void)hipEventDestroy(ev);
-    if (e->ev0) (void)hipEventDestroy(e->ev0);
-    if (e->ev1) (void)hipEventDestroy(e->ev1);
+    e->tm.destroy();
     delete e;
     return HM_OK;
 }
@@ -341,70 +337,17 @@ int64_t hm_pairs_in_range(int64_t n, int64_t r0, int64_t r1)
     return cnt * (n - 1) - (r0 + r1 - 1) * cnt / 2;
 }
 
-void hm_flush_pending_timing(hm_engine* e)
-{
-    if (!e->pending_timing) return;
-    float ms = 0.f;
-    if (hipEventSynchronize(e->ev1) == hipSuccess && hipEventElapsedTime(&ms, e->ev0, e->ev1) == hipSuccess) {
-        e->last_scan_ms = ms; e->last_pairs = e->pending_pairs; e->last_passes = 1;
-        e->tot_scan_ms += ms; e->tot_pairs += e->pending_pairs; e->tot_launches += 1;
-    }
-    e->pending_timing = false;
-}
-
-void hm_scan_stats_begin(hm_engine* e)
-{
-    hm_flush_pending_timing(e);
-    e->last_scan_ms = 0.f; e->last_pairs = 0; e->last_emitted = 0; e->last_passes = 0;
-}
-
-void hm_scan_stats_add(hm_engine* e, int64_t pairs, int64_t emitted)
-{
-    float ms = 0.f;
-    (void)hipEventElapsedTime(&ms, e->ev0, e->ev1);
-    e->last_scan_ms += ms;
-    e->last_passes += 1;
-    e->last_pairs = pairs;
-    e->tot_scan_ms += ms; e->tot_pairs += pairs; e->tot_launches += 1;
-    e->last_emitted = emitted;
-}
-
-// the per-scan event pairs of the last complete device batch (hm_debug_time_loops), read on demand
-void hm_read_loop_events(hm_engine* e)
-{
-    const int64_t steps = e->loop_unread_steps;
-    if (steps <= 0 || e->loop_evs.empty()) return;
-    e->loop_unread_steps = 0;
-    e->last_batch_ms = e->last_batch_scan_ms = 0.f;
-    float ms = 0.f;
-    if (hipEventElapsedTime(&ms, e->loop_evs[2 * HM_LOOP_MAX_STEPS], e->loop_evs[2 * HM_LOOP_MAX_STEPS + 1]) == hipSuccess) e->last_batch_ms = ms;
-    for (int64_t k = 0; k < steps; ++k) {
-        if (hipEventElapsedTime(&ms, e->loop_evs[2 * k], e->loop_evs[2 * k + 1]) != hipSuccess) continue;
-        e->last_batch_scan_ms += ms;
-        e->tot_scan_ms += ms; e->tot_pairs += e->loop_unread_pairs[k]; e->tot_launches += 1;
-    }
-    e->last_batch_steps = steps;
-}
-
 extern "C" int hm_last_scan_stats(const hm_engine* e, float* scan_ms, int64_t* pairs, int64_t* emitted, int32_t* passes)
 {
     if (!e) return HM_E_ARG;
-    if (scan_ms) *scan_ms = e->last_scan_ms;
-    if (pairs) *pairs = e->last_pairs;
-    if (emitted) *emitted = e->last_emitted;
-    if (passes) *passes = e->last_passes;
+    e->tm.last_scan(scan_ms, pairs, emitted, passes);
     return HM_OK;
 }
 
 extern "C" int hm_scan_totals(hm_engine* e, double* scan_ms, int64_t* pairs, int64_t* launches, int reset)
 {
     if (!e) return HM_E_ARG;
-    hm_flush_pending_timing(e);
-    hm_read_loop_events(e);
-    if (scan_ms) *scan_ms = e->tot_scan_ms;
-    if (pairs) *pairs = e->tot_pairs;
-    if (launches) *launches = e->tot_launches;
-    if (reset) { e->tot_scan_ms = 0.0; e->tot_pairs = 0; e->tot_launches = 0; }
+    e->tm.totals(scan_ms, pairs, launches, reset != 0);
     return HM_OK;
 }
 
@@ -424,20 +367,13 @@ extern "C" int hm_debug_time_loops(hm_engine* e, int on)
 {
     if (!e) return hm_fail(nullptr, HM_E_ARG, "hm_debug_time_loops: engine is NULL");
     HM_HIP(hipSetDevice(e->device));
-    if (on && e->loop_evs.empty()) {
-        e->loop_evs.resize(2 * HM_LOOP_MAX_STEPS + 2, nullptr);
-        for (auto& ev : e->loop_evs) HM_HIP(hipEventCreate(&ev));
-    }
-    e->time_loops = on != 0;
+    HM_HIP(e->tm.set_time_loops(on != 0));
     return HM_OK;
 }
 
 extern "C" int hm_last_loop_timing(hm_engine* e, float* batch_ms, float* scan_ms, int64_t* steps)
 {
     if (!e || !batch_ms || !scan_ms || !steps) return HM_E_ARG;
-    hm_read_loop_events(e);
-    *batch_ms = e->last_batch_ms;
-    *scan_ms = e->last_batch_scan_ms;
-    *steps = e->last_batch_steps;
+    e->tm.last_loop(batch_ms, scan_ms, steps);
     return HM_OK;
 }

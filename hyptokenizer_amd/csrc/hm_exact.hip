@@ -228,6 +228,6 @@ int hm_topk_exact(hm_engine* e, float c, float thr, int64_t k, int64_t row_begin
     if (e->h->ctr64[2] > (unsigned long long)e->ent_cap) return hm_fail(e, HM_E_CAPACITY, "exact search: emission count exceeds its own bound");
     *n_valid_emitted = (int64_t)e->h->ctr64[2];
     *result_dev = e->ent;
-    e->last_emitted = (int64_t)e->h->ctr64[2];
+    e->tm.set_emitted((int64_t)e->h->ctr64[2]);
     return HM_OK;
 }

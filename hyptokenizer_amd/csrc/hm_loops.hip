@@ -13,6 +13,7 @@
 // all blocks scan their slice of the image against it, and the last block to finish folds the new row's nearest
 // partner into the running minimum.
 #include "hm_common.h"
+#include "hm_batch_plan.h"
 #include "hm_rows_device.h"
 
 #pragma clang fp contract(off)
@@ -150,83 +151,103 @@ static int hm_pipeline_init(hm_engine* e)
     return HM_OK;
 }
 
-static int hm_std_merge_steps_pipelined(hm_engine* e, float c, float thr, const Bounds& b, float* X_dev, int64_t ld, int64_t steps, hipStream_t s,
-                                        int64_t* all_pairs, bool time_all, int64_t* timed_pairs)
+// what every step of a call shares
+struct StdLoop { float c, thr, sqrt_c; Bounds b; float* X; int64_t ld; hipStream_t s; uint32_t* rec_out; };
+
+// Step k of a segment of `count` steps, in either form; advances n and head_merges (optimistic: HmBatchGuard).
+// Sequential: the scan of the whole table, then the tail, on the caller's stream; `armed`: no seed-init launch.
+// Pipelined adds what is its own: buffer set k & 1, scan_old(k) under the order guard, rowpass(k) and tail(k) on aux.
+static int hm_issue_step(hm_engine* e, const StdLoop& L, int64_t k, int64_t count, bool piped, bool armed, int fault_at, size_t row_lds)
 {
-    int rc = hm_pipeline_init(e);
-    if (rc) return rc;
-    const int64_t n0 = e->n, hm0 = e->head_merges;
-    const float sqrt_c = sqrtf(c);
-    hipStream_t sb = e->aux;
-    // the tail stream starts behind everything the caller's stream holds so far (table, token lengths, loop state)
-    HM_HIP(hipMemsetAsync(e->d_rowkey, 0xff, sizeof(unsigned long long) * 2, s));
-    HM_HIP(hipEventRecord(e->ev_join, s));
-    HM_HIP(hipStreamWaitEvent(sb, e->ev_join, 0));
-    size_t row_lds = 0;
-    rc = hm_row_key_lds(e, &row_lds);
-    if (rc) return rc;
-    for (int64_t k = 0; k < steps; ++k) {
-        const int set = (int)(k & 1);
-        e->n = n0 + k;                                   // rows of step k's table (optimistic: corrected by the caller when the batch stops early)
-        e->head_merges = hm0 + k;                        // (which argmin kernel this step's scan gets: hm_head_live)
-        const int64_t n_old = k == 0 ? e->n : e->n - 1;  // scan_old(k): all rows but the newest (step 0: the whole table)
-        ScanArgs a; dim3 grid;
-        if (!hm_prepare_scan(e, b, 0, -1, a, grid, n_old)) return hm_fail(e, HM_E_STATE, "hm_std_merge_steps: empty scan");
-        a.stop = &e->d_loop->stop;
+    const int set = piped ? (int)(k & 1) : 0;
+    ScanArgs a; dim3 grid;
+    // (pipelined) scan_old(k): all rows but the newest (step 0: the whole table)
+    if (!hm_prepare_scan(e, L.b, 0, -1, a, grid, piped && k > 0 ? e->n - 1 : -1)) return hm_fail(e, HM_E_STATE, "hm_std_merge_steps: empty scan");
+    a.stop = &e->d_loop->stop;
+    if (piped) {
         a.ent = set ? e->ent2 : e->ent;
         a.ctr64 = e->d_ctr64 + 4 * set;
-        // ---- caller's stream: scan_old(k) ----
-        if (k == 0) {
-            // both sets armed from the engine's seed before any tail runs (later steps: their set is armed by tail(k - 2))
-            ScanArgs a1 = a;
-            a1.ctr64 = e->d_ctr64 + 4;
-            rc = hm_launch_seed_init(e, a, s);
-            if (rc == HM_OK) rc = hm_launch_seed_init(e, a1, s);
-            if (rc) return rc;
-        } else if (k >= 2) {
-            // tail(k - 2) wrote this scan's newest row and armed its counters a whole scan ago, on the other stream: checked
-            // by the scan's blocks themselves (ScanArgs::order_*), not waited for with an event on this stream
-            a.order_seen = &e->d_loop->tails_done;
-            a.order_need = (uint32_t)(k - 1) + (e->pipe_fault_at == (int)k ? 1000000u : 0u);
-            a.order_fault = &e->d_loop->stop;
-        }
-        // The scan's completion event rides IN its dispatch (the kernel's own completion signal: no extra packet on this
-        // stream, where an hipEventRecord costs a 6 us bubble): the tail stream waits for that event.
-        const bool timed = (k == steps - 1);
-        hipEvent_t ev_start = nullptr, ev_stop = e->ev_scan[set];
-        if (time_all) {
-            if (k == 0) HM_HIP(hipEventRecord(e->loop_evs[2 * HM_LOOP_MAX_STEPS], s));
-            ev_start = e->loop_evs[2 * k]; ev_stop = e->loop_evs[2 * k + 1];
-            all_pairs[k] = hm_pairs_in_range(e->n, 0, e->n - 1);
-        } else if (timed) {
-            ev_start = e->ev0; ev_stop = e->ev1;
-        }
-        HM_HIP(hm_launch_scan(e, HM_MODE_ARGMIN, a, grid, s, ev_start, ev_stop));
-        if (timed) *timed_pairs = hm_pairs_in_range(e->n, 0, e->n - 1);
+    }
+    if (piped && k == 0) {
+        // both sets armed from the engine's seed before any tail runs (later steps: their set is armed by tail(k - 2))
+        ScanArgs a1 = a;
+        a1.ctr64 = e->d_ctr64 + 4;
+        int rc = hm_launch_seed_init(e, a, L.s);
+        if (rc == HM_OK) rc = hm_launch_seed_init(e, a1, L.s);
+        if (rc) return rc;
+    } else if (piped && k >= 2) {
+        // tail(k - 2) wrote this scan's newest row and armed its counters a whole scan ago, on the other stream: checked
+        // by the scan's blocks themselves (ScanArgs::order_*), not waited for with an event on this stream
+        a.order_seen = &e->d_loop->tails_done;
+        a.order_need = (uint32_t)(k - 1) + (fault_at == (int)k ? 1000000u : 0u);
+        a.order_fault = &e->d_loop->stop;
+    } else if (!piped && !armed) {
+        if (const int rc = hm_launch_seed_init(e, a, L.s)) return rc;
+    }
+    // the last scan of the segment carries the engine's timing events (one pair per engine); in the measurement mode of
+    // hm_debug_time_loops every scan has its own pair.  Pipelined, the scan's completion event rides IN its dispatch (the
+    // kernel's own completion signal: no extra packet on this stream, where an hipEventRecord costs a 6 us bubble): the
+    // tail stream waits for that event.
+    HmEvPair ev;
+    HM_HIP(e->tm.scan_events(k, k == count - 1, hm_pairs_in_range(e->n, 0, e->n - 1), L.s, &ev));
+    if (piped && !ev.ev1) ev.ev1 = e->ev_scan[set];
+    HM_HIP(hm_launch_scan(e, HM_MODE_ARGMIN, a, grid, L.s, ev.ev0, ev.ev1));
+    MergeFuse mf;
+    memset(&mf, 0, sizeof(mf));
+    mf.X = L.X; mf.ld = L.ld; mf.new_row = e->n; mf.c = L.c;
+    mf.len = e->d_len; mf.len_rw = e->d_len; mf.loop = e->d_loop; mf.rec_ring = e->d_loop_recs + k;
+    hipStream_t st = L.s;
+    if (piped) {
         // ---- tail stream: rowpass(k) (behind tail(k - 1)), then tail(k) behind scan_old(k) ----
+        st = e->aux;
         if (k >= 1) {
             const int64_t row = e->n - 1;
             const int64_t nt = (row + HM_TILE_ROWS - 1) / HM_TILE_ROWS;
-            hipLaunchKernelGGL(hm_newrow_key_kernel, dim3((unsigned)std::max<int64_t>(1, std::min<int64_t>(nt, 128))), dim3(64), row_lds, sb, e->img, e->RS,
-                               e->d, row, row, sqrt_c, thr, e->sign_mode, e->d_rowkey + set, &e->d_loop->stop);
+            hipLaunchKernelGGL(hm_newrow_key_kernel, dim3((unsigned)std::max<int64_t>(1, std::min<int64_t>(nt, 128))), dim3(64), row_lds, st, e->img, e->RS,
+                               e->d, row, row, L.sqrt_c, L.thr, e->sign_mode, e->d_rowkey + set, &e->d_loop->stop);
             HM_HIP(hipGetLastError());
         }
-        HM_HIP(hipStreamWaitEvent(sb, ev_stop, 0));
-        MergeFuse mf;
-        memset(&mf, 0, sizeof(mf));
-        mf.X = X_dev; mf.ld = ld; mf.new_row = e->n; mf.c = c;
-        mf.len = e->d_len; mf.len_rw = e->d_len; mf.loop = e->d_loop; mf.rec_ring = e->d_loop_recs + k;
+        HM_HIP(hipStreamWaitEvent(st, ev.ev1, 0));
         mf.pipe_ent = a.ent; mf.pipe_ctr64 = a.ctr64;
         mf.rowkey = e->d_rowkey + set; mf.rowkey_j = (uint32_t)(e->n - 1);
-        rc = hm_launch_argmin_tail(e, a, sqrt_c, thr, e->d_rec, true, 0, 0x7fffffff, true, mf, sb);
-        if (rc) return rc;
-        HM_HIP(hipEventRecord(e->ev_tail[set], sb));
     }
-    e->n = n0 + steps;
-    e->head_merges = hm0;                                // (the caller counts the steps that merged)
-    // the caller's stream continues behind the last tails
-    HM_HIP(hipStreamWaitEvent(s, e->ev_tail[(steps - 1) & 1], 0));
-    if (steps >= 2) HM_HIP(hipStreamWaitEvent(s, e->ev_tail[(steps - 2) & 1], 0));
+    if (const int rc = hm_launch_argmin_tail(e, a, L.sqrt_c, L.thr, e->d_rec, true, 0, 0x7fffffff, true, mf, st)) return rc;
+    if (piped) HM_HIP(hipEventRecord(e->ev_tail[set], st));
+    e->n += 1;
+    e->head_merges += 1;                                 // (which argmin kernel the next step's scan gets: hm_head_live)
+    return HM_OK;
+}
+
+// One segment of a batch (hm_batch_plan.h), begun the way a call begins: LoopState zeroed, record slots [0, count) reused
+// and unpacked to the segment's place in rec_out.  *merged = its leading steps that merged, *stop = the loop's stop word
+// (read for a pipelined segment only).
+static int hm_issue_segment(hm_engine* e, const StdLoop& L, const BatchSegment& seg, bool piped, bool armed, int fault_at, int64_t* merged,
+                            uint32_t* stop)
+{
+    hipStream_t s = L.s;
+    HM_HIP(hipMemsetAsync(e->d_loop, 0, sizeof(LoopState), s));
+    e->tm.begin_segment();
+    size_t row_lds = 0;
+    if (piped) {
+        if (const int rc = hm_pipeline_init(e)) return rc;
+        // the tail stream starts behind everything the caller's stream holds so far (table, token lengths, loop state)
+        HM_HIP(hipMemsetAsync(e->d_rowkey, 0xff, sizeof(unsigned long long) * 2, s));
+        HM_HIP(hipEventRecord(e->ev_join, s));
+        HM_HIP(hipStreamWaitEvent(e->aux, e->ev_join, 0));
+        if (const int rc = hm_row_key_lds(e, &row_lds)) return rc;
+    }
+    for (int64_t k = 0; k < seg.count; ++k)
+        if (const int rc = hm_issue_step(e, L, k, seg.count, piped, armed || k > 0, fault_at, row_lds)) return rc;
+    if (piped) {                                         // the caller's stream continues behind the last tails
+        HM_HIP(hipStreamWaitEvent(s, e->ev_tail[(seg.count - 1) & 1], 0));
+        HM_HIP(hipStreamWaitEvent(s, e->ev_tail[(seg.count - 2) & 1], 0));
+    }
+    HM_HIP(e->tm.end_segment(s));
+    HM_HIP(hipMemcpyAsync(e->h->loop_recs, e->d_loop_recs, sizeof(ArgminRec) * (size_t)seg.count, hipMemcpyDeviceToHost, s));
+    if (piped) HM_HIP(hipMemcpyAsync(&e->h->ctr[7], &e->d_loop->stop, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    HM_HIP(hipStreamSynchronize(s));
+    hm_unpack_recs(e->h->loop_recs, seg.count, L.rec_out + 4 * seg.first_step, merged);
+    *stop = piped ? e->h->ctr[7] : 0u;
     return HM_OK;
 }
 
@@ -243,118 +264,40 @@ extern "C" int hm_std_merge_steps(hm_engine* e, float c, float thr, float* X_dev
     *done = 0;
     if (steps == 0) return HM_OK;
     if (e->n + steps > e->max_rows) return hm_fail(e, HM_E_CAPACITY, "hm_std_merge_steps: the table cannot take that many rows");
-    hipStream_t s = (hipStream_t)stream;
     HM_HIP(hipSetDevice(e->device));
-    hm_flush_pending_timing(e);
-    const Bounds b = hm_bounds(thr, c);
-    if (b.none || e->n < 2) {                 // nothing can be below the threshold
+    e->tm.flush_pending();
+    const StdLoop L = {c, thr, sqrtf(c), hm_bounds(thr, c), X_dev, ld, (hipStream_t)stream, rec_out};
+    if (L.b.none || e->n < 2) {                 // nothing can be below the threshold
         for (int64_t k = 0; k < steps; ++k) { rec_out[4 * k] = k == 0 ? 0u : 3u; rec_out[4 * k + 1] = 0; rec_out[4 * k + 2] = rec_out[4 * k + 3] = 0xffffffffu; }
         return HM_OK;
     }
-    const int64_t n0 = e->n, hm0 = e->head_merges;
-    const float sqrt_c = sqrtf(c);
-    HM_HIP(hipMemsetAsync(e->d_loop, 0, sizeof(LoopState), s));
+    HmBatchGuard guard(e);
+    // the first segment alone starts on what the previous call left: its arming, and the test hook's order fault
     bool armed = e->st.take_arm(0, -1);
-    int64_t timed_pairs = 0;
-    const bool time_all = e->time_loops && !e->loop_evs.empty();
-    if (time_all) hm_read_loop_events(e);         // the events are about to be reused
-    int64_t all_pairs[HM_LOOP_MAX_STEPS];
-    // pipelined when a scan is long against a tail kernel (the tail of step k - 2 has to be through while scan k - 1 runs; the
-    // scans' order guard catches the rest): from ~30 000 rows on (hm_engine::pipeline_min_pairs)
-    const bool piped = e->pipeline && steps >= 2 && hm_pairs_in_range(e->n, 0, e->n - 1) >= e->pipeline_min_pairs;
-    if (piped) {
-        const int rcp = hm_std_merge_steps_pipelined(e, c, thr, b, X_dev, ld, steps, s, all_pairs, time_all, &timed_pairs);
-        if (rcp) { (void)hipStreamSynchronize(s); if (e->aux) (void)hipStreamSynchronize(e->aux); e->n = n0; e->head_merges = hm0; return rcp; }
-    }
-    for (int64_t k = 0; k < (piped ? 0 : steps); ++k) {
-        ScanArgs a; dim3 grid;
-        if (!hm_prepare_scan(e, b, 0, -1, a, grid)) return hm_fail(e, HM_E_STATE, "hm_std_merge_steps: empty scan");
-        a.stop = &e->d_loop->stop;
-        if (!armed) {
-            int rc0 = hm_launch_seed_init(e, a, s);
-            if (rc0) { e->n = n0; e->head_merges = hm0; return rc0; }
+    int fault_at = e->pipe_fault_at;
+    BatchPlan plan(steps);
+    while (plan.pending()) {
+        const BatchSegment seg = plan.segment();
+        // pipelined when a scan is long against a tail kernel (the tail of step k - 2 has to be through while scan k - 1 runs; the
+        // scans' order guard catches the rest): from ~30 000 rows on (hm_engine::pipeline_min_pairs)
+        const bool piped = seg.may_pipeline && e->pipeline && seg.count >= 2 && hm_pairs_in_range(e->n, 0, e->n - 1) >= e->pipeline_min_pairs;
+        int64_t merged = 0;
+        uint32_t stop = 0;
+        if (const int rc = hm_issue_segment(e, L, seg, piped, armed, fault_at, &merged, &stop)) {
+            if (piped) { (void)hipStreamSynchronize(L.s); if (e->aux) (void)hipStreamSynchronize(e->aux); }
+            return rc;
         }
-        // the last scan of the batch carries the timing events (one event pair per engine); in the measurement mode of
-        // hm_debug_time_loops every scan has its own pair
-        const bool timed = (k == steps - 1);
-        if (time_all) {
-            if (k == 0) HM_HIP(hipEventRecord(e->loop_evs[2 * HM_LOOP_MAX_STEPS], s));
-            HM_HIP(hm_launch_scan(e, HM_MODE_ARGMIN, a, grid, s, e->loop_evs[2 * k], e->loop_evs[2 * k + 1]));
-            all_pairs[k] = hm_pairs_in_range(e->n, a.row_begin, a.row_end);
-        } else {
-            HM_HIP(hm_launch_scan(e, HM_MODE_ARGMIN, a, grid, s, timed ? e->ev0 : nullptr, timed ? e->ev1 : nullptr));
-        }
-        if (timed) timed_pairs = hm_pairs_in_range(e->n, a.row_begin, a.row_end);
-        MergeFuse mf;
-        memset(&mf, 0, sizeof(mf));
-        mf.X = X_dev; mf.ld = ld; mf.new_row = e->n; mf.c = c;
-        mf.len = e->d_len; mf.len_rw = e->d_len; mf.loop = e->d_loop; mf.rec_ring = e->d_loop_recs + k;
-        int rc = hm_launch_argmin_tail(e, a, sqrt_c, thr, e->d_rec, true, 0, 0x7fffffff, true, mf, s);
-        if (rc) { e->n = n0; e->head_merges = hm0; return rc; }
-        armed = true;
-        e->n += 1;                            // optimistic: corrected below when the batch stopped early
-        e->head_merges += 1;
-    }
-    if (time_all) HM_HIP(hipEventRecord(e->loop_evs[2 * HM_LOOP_MAX_STEPS + 1], s));
-    HM_HIP(hipMemcpyAsync(e->h->loop_recs, e->d_loop_recs, sizeof(ArgminRec) * (size_t)steps, hipMemcpyDeviceToHost, s));
-    if (piped) HM_HIP(hipMemcpyAsync(&e->h->ctr[7], &e->d_loop->stop, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-    HM_HIP(hipStreamSynchronize(s));
-    hm_unpack_recs(e->h->loop_recs, steps, rec_out, done);
-    e->n = n0 + *done;
-    e->head_merges = hm0 + *done;
-    if (piped && *done < steps && e->h->ctr[7] == 5u) {
-        // a scan's order guard tripped (never seen outside the test hook): the steps from there on, strictly sequentially
-        e->st.disarm();
-        e->pipe_fault_at = -1;
-        const HmScopedSet<bool> sequential(e->pipeline, false);
-        int64_t done2 = 0;
-        const int rc2 = hm_std_merge_steps(e, c, thr, X_dev, ld, steps - *done, rec_out + 4 * *done, &done2, stream);
-        if (rc2) return rc2;
-        *done += done2;
-        return HM_OK;
-    }
-    if (piped && *done < steps && e->h->ctr[7] == 6u) {
-        // a step left more survivors than the pipelined tail's small grid takes (typically the first search on a new table,
-        // before a seed bounds the emissions): that ONE step through the sequential chain and its full-size tail, the rest
-        // pipelined again
-        e->st.disarm();
-        int64_t done2 = 0;
-        int rc2;
-        {
-            const HmScopedSet<bool> sequential(e->pipeline, false);
-            rc2 = hm_std_merge_steps(e, c, thr, X_dev, ld, 1, rec_out + 4 * *done, &done2, stream);
-        }
-        if (rc2) return rc2;
-        *done += done2;
-        if (done2 == 1 && *done < steps) {
-            const int64_t before = *done;
-            int64_t done3 = 0;
-            rc2 = hm_std_merge_steps(e, c, thr, X_dev, ld, steps - before, rec_out + 4 * before, &done3, stream);
-            if (rc2) return rc2;
-            *done = before + done3;
-        }
-        return HM_OK;
+        guard.confirm(merged);
+        e->tm.commit_segment(seg.count, merged == seg.count);
+        plan.report(piped, merged, stop);
+        armed = false;
+        fault_at = -1;
     }
     e->pipe_fault_at = -1;
-    if (*done == steps && !piped) e->st.arm(0, -1); // (the pipelined batch leaves its two sets armed for ITS next steps only)
+    if (plan.leaves_armed()) e->st.arm(0, -1);
     else e->st.disarm();
-    if (time_all) {
-        e->last_batch_ms = e->last_batch_scan_ms = 0.f;
-        e->last_batch_steps = 0;
-        if (*done == steps) {                     // read later (hm_read_loop_events): not in the call being timed
-            e->loop_unread_steps = steps;
-            e->loop_unread_pairs.assign(all_pairs, all_pairs + steps);
-        }
-        return HM_OK;
-    }
-    if (*done == steps) {
-        float ms = 0.f;
-        if (hipEventElapsedTime(&ms, e->ev0, e->ev1) == hipSuccess) {
-            // one launch of the batch is timed; the totals count it once (bench: mean launch duration)
-            e->last_scan_ms = ms; e->last_pairs = timed_pairs; e->last_passes = 1;
-            e->tot_scan_ms += ms; e->tot_pairs += timed_pairs; e->tot_launches += 1;
-        }
-    }
+    guard.commit();
+    *done = plan.done();
     return HM_OK;
 }
 
@@ -517,7 +460,7 @@ extern "C" int hm_incr_merge_steps(hm_engine* e, float c, float thr, float* X_de
         fin.found = 0u;
     }
     best_io[0] = fin.found; best_io[1] = fin.dbits; best_io[2] = fin.i; best_io[3] = fin.j;
-    e->n = n0 + *done;
+    e->n += *done;                                // (nothing was advanced while the steps were enqueued)
     return HM_OK;
 }
 

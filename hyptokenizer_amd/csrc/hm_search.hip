@@ -542,7 +542,7 @@ static int hm_estimate_cut(hm_engine* e, ScanArgs a, dim3 grid, int64_t target, 
         HM_HIP(hm_launch_scan(e, HM_MODE_HIST, a, grid, s));
         HM_HIP(hipMemcpyAsync(e->h->hist, e->d_hist, sizeof(uint32_t) * HM_HIST_BINS, hipMemcpyDeviceToHost, s));
         HM_HIP(hipStreamSynchronize(s));
-        e->last_passes += 1;
+        e->tm.count_pass();
         double cum = base;
         int bsel = -1;
         for (int q = 0; q < HM_HIST_BINS; ++q) {
@@ -616,7 +616,7 @@ static int hm_topk_core_form(hm_engine* e, float c, float thr, int64_t k, int64_
     *n_valid_emitted = 0;
     *count = 0;
     *result_dev = nullptr;
-    hm_scan_stats_begin(e);
+    e->tm.begin_search();
     const Bounds b = hm_bounds(thr, c);
     ScanArgs a; dim3 grid;
     if (b.none || e->n < 2 || !hm_prepare_scan(e, b, row_begin, row_end, a, grid, n_limit)) return HM_OK;
@@ -649,14 +649,14 @@ static int hm_topk_core_form(hm_engine* e, float c, float thr, int64_t k, int64_
         a.tie_imax = tie_imax;
         HM_HIP(hipMemsetAsync(e->d_ctr, 0, sizeof(uint32_t) * 8, s));
         HM_HIP(hipMemsetAsync(e->d_ctr64, 0, sizeof(unsigned long long) * 4, s));
-        HM_HIP(hm_launch_scan(e, HM_MODE_TOPK, a, grid, s, e->ev0, e->ev1));
+        HM_HIP(hm_launch_scan(e, HM_MODE_TOPK, a, grid, s, e->tm.own().ev0, e->tm.own().ev1));
         hipLaunchKernelGGL(hm_post_distance_kernel, dim3(1024), dim3(256), 0, s, e->ent, e->d_ctr64, e->ent_cap, e->img, e->RS, e->d,
                            e->sign_mode, sqrt_c, thr, cut_bits, tie_imax, e->d_ctr + 1);
         HM_HIP(hipGetLastError());
         HM_HIP(hipMemcpyAsync(e->h->ctr, e->d_ctr, sizeof(uint32_t) * 8, hipMemcpyDeviceToHost, s));
         HM_HIP(hipMemcpyAsync(e->h->ctr64, e->d_ctr64, sizeof(unsigned long long) * 4, hipMemcpyDeviceToHost, s));
         HM_HIP(hipStreamSynchronize(s));
-        hm_scan_stats_add(e, hm_pairs_in_range(a.n, a.row_begin, a.row_end), (int64_t)e->h->ctr64[2]);
+        e->tm.add_pass(hm_pairs_in_range(a.n, a.row_begin, a.row_end), (int64_t)e->h->ctr64[2]);
         if (e->h->ctr[4] != 0)
             return hm_fail(e, HM_E_STATE, "pair scan: prefilter margin violated (an entry classified as surely below the "
                                           "threshold is not); table holds non-finite rows other than all-NaN rows?");
@@ -730,7 +730,7 @@ extern "C" int hm_pairwise_argmin_dev(hm_engine* e, float c, float thr, int64_t 
     if (!(c > 0.0f)) return hm_fail(e, HM_E_ARG, "hm_pairwise_argmin_dev: curvature must be > 0");
     hipStream_t s = (hipStream_t)stream;
     HM_HIP(hipSetDevice(e->device));
-    hm_flush_pending_timing(e);
+    e->tm.flush_pending();
     const Bounds b = hm_bounds(thr, c);
     ScanArgs a; dim3 grid;
     const int64_t req_rb = std::max<int64_t>(row_begin, 0), req_re = (row_end < 0 || row_end >= e->n) ? -1 : row_end;
@@ -750,11 +750,11 @@ extern "C" int hm_pairwise_argmin_dev(hm_engine* e, float c, float thr, int64_t 
     }
     // (inside a sharded loop only the batch's first search carries the engine's own timing events: reading them back at the
     // next call is a host wait, and the point of the loop is that the host runs ahead of the device; the in-library loop in
-    // its measurement mode hands every step its own pair -- e->step_ev0 / _ev1, read after the batch)
-    const bool step_timed = e->step_ev0 != nullptr;
-    const bool timed = !step_timed && (!e->shard_loop || e->n == e->shard_n0);
-    HM_HIP(hm_launch_scan(e, HM_MODE_ARGMIN, a, grid, s, step_timed ? e->step_ev0 : (timed ? e->ev0 : nullptr),
-                          step_timed ? e->step_ev1 : (timed ? e->ev1 : nullptr)));
+    // its measurement mode opens every step's own pair -- ScanTiming::open_step, read after the batch)
+    const HmEvPair step = e->tm.step_pair();
+    const bool timed = !step.ev0 && (!e->shard_loop || e->n == e->shard_n0);
+    const HmEvPair ev = timed ? e->tm.own() : step;
+    HM_HIP(hm_launch_scan(e, HM_MODE_ARGMIN, a, grid, s, ev.ev0, ev.ev1));
     int rc = hm_launch_argmin_tail(e, a, sqrtf(c), thr, reinterpret_cast<ArgminRec*>(rec_dev), true, (int)req_rb,
                                    req_re < 0 ? 0x7fffffff : (int)std::min<int64_t>(req_re, 0x7fffffff), true, mf, s);
     if (rc) return rc;
@@ -762,10 +762,7 @@ extern "C" int hm_pairwise_argmin_dev(hm_engine* e, float c, float thr, int64_t 
     // kernel then arms nothing), the next search of this range starts on the stale counters, reports found = 2 as
     // well, and its caller takes the bounded host path -- slower, never wrong.
     e->st.arm(req_rb, req_re);
-    if (timed) {
-        e->pending_timing = true;
-        e->pending_pairs = hm_pairs_in_range(e->n, a.row_begin, a.row_end);
-    }
+    if (timed) e->tm.note_pending(hm_pairs_in_range(e->n, a.row_begin, a.row_end));
     return HM_OK;
 }
 
@@ -778,7 +775,7 @@ extern "C" int hm_pairwise_argmin(hm_engine* e, float c, float thr, int64_t row_
     hipStream_t s = (hipStream_t)stream;
     HM_HIP(hipSetDevice(e->device));
     *found = 0; *d = 0.f; *i = -1; *j = -1;
-    hm_scan_stats_begin(e);
+    e->tm.begin_search();
     const Bounds b = hm_bounds(thr, c);
     ScanArgs a; dim3 grid;
     // the range as asked, "to the end" normalised (the table grows between searches): what "same range" means
@@ -806,7 +803,7 @@ extern "C" int hm_pairwise_argmin(hm_engine* e, float c, float thr, int64_t row_
         } else {
             HM_HIP(hipMemsetAsync(e->d_ctr64 + 2, 0, sizeof(unsigned long long), s));     // emitted = 0, running key kept
         }
-        HM_HIP(hm_launch_scan(e, HM_MODE_ARGMIN, a, grid, s, e->ev0, e->ev1));
+        HM_HIP(hm_launch_scan(e, HM_MODE_ARGMIN, a, grid, s, e->tm.own().ev0, e->tm.own().ev1));
         int rc = hm_launch_argmin_tail(e, a, sqrt_c, thr, e->d_rec, true, (int)req_rb, arm_re, true, kNoMerge, s);
         if (rc) return rc;
         // record + emitted count (the slot behind the record) in one copy
@@ -814,7 +811,7 @@ extern "C" int hm_pairwise_argmin(hm_engine* e, float c, float thr, int64_t row_
         HM_HIP(hipStreamSynchronize(s));
         e->h->rec = e->h->rec2[0];
         const uint64_t emitted = (uint64_t)e->h->rec2[1].found | ((uint64_t)e->h->rec2[1].dbits << 32);
-        hm_scan_stats_add(e, hm_pairs_in_range(e->n, a.row_begin, a.row_end), (int64_t)emitted);
+        e->tm.add_pass(hm_pairs_in_range(e->n, a.row_begin, a.row_end), (int64_t)emitted);
         if (emitted <= e->ent_cap) break;
         // overflow: the running key is the exact minimum over all published waves; rerun bounded by it
         if (pass == 1) {
@@ -858,7 +855,7 @@ static uint32_t hm_topk_incremental_limit(const hm_engine* e) { return std::min<
 // everything of the incremental refresh up to the read-back, enqueued; no host wait
 static int hm_topk_incremental_enqueue(hm_engine* e, float c, float thr, int64_t k, hipStream_t s)
 {
-    hm_scan_stats_begin(e);
+    e->tm.begin_search();
     const Bounds b = hm_bounds(thr, c);
     const uint32_t lim = hm_topk_incremental_limit(e);
     if ((uint64_t)k + 1 > lim) return HM_E_CAPACITY;
@@ -874,7 +871,7 @@ static int hm_topk_incremental_enqueue(hm_engine* e, float c, float thr, int64_t
         hipLaunchKernelGGL(hm_post_distance_kernel, dim3(256), dim3(256), 0, s, e->ent, e->d_ctr64, e->ent_cap, e->img, e->RS, e->d,
                            e->sign_mode, sqrtf(c), thr, a.cut_bits, a.tie_imax, e->d_ctr + 1);
         HM_HIP(hipGetLastError());
-        e->last_passes = 1;
+        e->tm.count_pass();
     }
     // union with the previous list (appended behind the new entries; invalid new entries carry all-ones keys), sorted
     // outright: the count of new entries stays on the device
@@ -896,7 +893,7 @@ static int hm_topk_incremental_finish(hm_engine* e, int64_t k, hipStream_t s, ui
 {
     *kk_out = 0;
     HM_HIP(hipStreamSynchronize(s));
-    e->last_emitted = (int64_t)e->h->ctr64[2];
+    e->tm.set_emitted((int64_t)e->h->ctr64[2]);
     if (e->h->ctr64[2] > (unsigned long long)(hm_topk_incremental_limit(e) - (uint32_t)k)) return HM_E_CAPACITY;
     *kk_out = (uint32_t)k;
     return HM_OK;
