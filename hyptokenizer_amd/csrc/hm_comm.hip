@@ -248,23 +248,21 @@ extern "C" int hm_global_topk(hm_engine* e, float c, float thr, int64_t k, float
     int64_t r0 = 0, r1 = 0;
     hm_partition_rows(e->n, e->world, e->rank, &r0, &r1);
     // this rank's ordered list stays on the device (e->sorted); its exact candidate count comes back with it
-    int64_t valid = 0, total = 0;
-    uint4* res = nullptr;
+    TopkResult res = {nullptr, 0u, 0, 0};
     uint32_t kk = 0;
     if (r1 > r0) {
-        int rc = hm_topk_core(e, c, thr, k, r0, r1, false, true, -1, &valid, &total, &res, s);
+        int rc = hm_topk_core(e, c, thr, k, r0, r1, false, true, -1, &res, s);
         if (rc) return rc;
-        kk = (uint32_t)std::min<int64_t>(k, valid);
-        if (kk > 0 && res) {
-            const uint32_t m = (uint32_t)std::min<uint64_t>(e->h->ctr64[2], e->ent_cap);
-            rc = hm_select_sorted(e, res, e->ent2, m, kk, s);
+        kk = (uint32_t)std::min<int64_t>(k, res.valid);
+        if (kk > 0 && res.ent) {
+            rc = hm_select_sorted(e, res.ent, e->ent2, res.m, kk, s);
             if (rc) return rc;
         }
     }
     e->st.drop_list();                                       // (range searches do not feed the whole-table refresh state)
     uint4* mine = e->d_gather;                               // [k + 1] packed list of this rank, then [world][k + 1] gathered
     uint4* all = e->d_gather + (k + 1);
-    hipLaunchKernelGGL(hm_gather_pack_kernel, dim3(64), dim3(256), 0, s, e->sorted, kk, (uint32_t)k, (unsigned long long)total, mine);
+    hipLaunchKernelGGL(hm_gather_pack_kernel, dim3(64), dim3(256), 0, s, e->sorted, kk, (uint32_t)k, (unsigned long long)res.total, mine);
     HM_HIP(hipGetLastError());
     HM_NCCL(R->AllGather(mine, all, (size_t)(k + 1) * 4, ncclInt32, reinterpret_cast<ncclComm_t>(e->comm), s));
     // headers (entries, counts) of all ranks: one small read-back decides how many entries the merged list has
@@ -283,10 +281,7 @@ extern "C" int hm_global_topk(hm_engine* e, float c, float thr, int64_t k, float
     if (rc) return rc;
     HM_HIP(hipMemcpyAsync(e->h_sorted, e->sorted, sizeof(uint4) * (size_t)want, hipMemcpyDeviceToHost, s));
     HM_HIP(hipStreamSynchronize(s));
-    for (uint32_t t = 0; t < want; ++t) {
-        union { uint32_t u; float f; } cv; cv.u = e->h_sorted[t].x;
-        d_out[t] = cv.f; i_out[t] = (int32_t)e->h_sorted[t].y; j_out[t] = (int32_t)e->h_sorted[t].z;
-    }
+    hm_unpack_entries(e->h_sorted, want, d_out, i_out, j_out);
     *n_out = want;
     return HM_OK;
 }

@@ -4,6 +4,8 @@
 //   hm_state.h      the search state carried from call to call and its named transitions (host)
 //   hm_timing.h     scan timing and statistics, one owner (host)
 //   hm_batch_plan.h the standard loop's redo policy: which steps are issued next, in which form (host, no HIP)
+//   hm_cut_plan.h   the top-k search's emission cut: which pass comes next, with which cut (host, no HIP)
+//   hm_tie_slack.h  hm_tie_slack, the one function the kernels and hm_cut_plan.h share
 //   hm_scan.hip     the pair-scan kernel (MFMA prefilter) and its launch  (hot kernel)
 //   hm_search.hip   exact re-evaluation / selection kernels and the search entry points of the ABI
 //   hm_rows.hip     the engine's row work: image construction, merge / midpoint, one-row-vs-all and gathered distances
@@ -49,6 +51,7 @@
 #include "../../include/hypmerge.h"
 #include "hm_device_math.h"
 #include "hm_state.h"
+#include "hm_tie_slack.h"
 
 #pragma clang fp contract(off)
 
@@ -60,7 +63,6 @@ typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 // ------------------------------------------------------------------------------------------------
 #define HM_MAX_BLOCK_ROWS 1024
 #define HM_MAX_D1 132              // largest table width (d + 1 <= 129) rounded up
-#define HM_TIE_SLACK 1024u         // ulps of u' that are treated as "may still order before" for u' >= 2 (see hm_tie_slack)
 #define HM_MODE_TOPK 0
 #define HM_MODE_ARGMIN 1
 #define HM_MODE_HIST 2
@@ -137,7 +139,7 @@ struct ScanArgs {
     int count_sure;               // TOPK mode: 1 = count every candidate (exact total); 0 = only what the cut asks for is visited
     uint4* ent;
     uint32_t ent_cap;
-    unsigned long long* ctr64;    // [0] sure count  [1] running best key (argmin)  [2] emitted entries  [3] spare
+    unsigned long long* ctr64;    // a counter set (HmCtr64 below): sure count, running best key (argmin), emitted entries, spare
     uint32_t* hist;               // HIST mode: HM_HIST_BINS bins
     uint32_t hist_lo;
     uint32_t hist_shift;
@@ -181,9 +183,27 @@ struct ArgminRec { uint32_t found, dbits, i, j; };      // found: 0 none, 1 pair
 struct ArgminPart { uint32_t dbits, i, j, pad; };
 struct Prefix { uint32_t val[3]; uint32_t mask[3]; };
 
+// the engine's small counters: d_ctr[8] / d_ctr64[4] on the device, HostCtl::ctr / ctr64 their pinned host mirror
+enum HmCtr {
+    HM_CTR_VALID = 1,            // hm_post_distance_kernel (it receives d_ctr + HM_CTR_POST_FIRST): emitted entries below the threshold
+    HM_CTR_BORDERLINE = 2,       //   ... that the prefilter was not sure of
+    HM_CTR_COMPACTED = 3,        // output count of the compaction kernels
+    HM_CTR_MARGIN_BAD = 4,       // hm_post_distance_kernel: sure entries that are not valid (must be 0)
+    HM_CTR_COMPLETE = 5,         //   valid entries of the complete region
+    HM_CTR_TAIL_TICKET = 6,      // argmin tail: arrival ticket of its blocks (device only)
+    HM_CTR_LOOP_STOP = 7,        // host mirror only: the pipelined loop's stop word (LoopState::stop)
+    HM_CTR_POST_FIRST = HM_CTR_VALID
+};
+enum HmCtr64 {
+    HM_CTR64_SURE = 0,           // pairs the scan counted as surely below the threshold
+    HM_CTR64_ARGMIN_KEY = 1,     // argmin: the running best key
+    HM_CTR64_EMITTED = 2,        // entries the scan emitted (may exceed the buffer)
+    HM_CTR64_ROW_KEY = 3         // host mirror only: hm_row_argmin's key
+};
+
 struct HostCtl {                 // pinned host mirror of small device results
-    uint32_t ctr[8];             // [1] valid [2] valid & !sure [3] compacted [4] margin violations [5] complete-region count
-    unsigned long long ctr64[4]; // [0] sure count [1] argmin key [2] emitted
+    uint32_t ctr[8];             // HmCtr
+    unsigned long long ctr64[4]; // HmCtr64
     ArgminRec rec;
     ArgminRec rec2[2];           // [0] record, [1].found / .dbits = emitted count (low / high)
     ArgminRec loop_recs[HM_LOOP_MAX_STEPS];
@@ -503,18 +523,6 @@ __device__ __forceinline__ float hm_halfwave_gather(int lane, UF u_of)
     return mine;
 }
 
-// How many ulps of u' above a key may still order BEFORE it by computed distance: d = acosh(u') / sqrt(c) is monotone in u' only
-// up to the few-ulp error of acosh (2.5 ulps of d), so a pair at u' + s certainly has the larger d once the true increase
-// s * ulp(u') / sqrt(u'^2 - 1) exceeds ~5 ulps of d.  For large u' (d ~ ln 2u') that takes up to 16 d ~ hundreds of ulps of u'
-// -- HM_TIE_SLACK; near u' = 1 (d ~ sqrt(2 (u' - 1)), steep) a handful do: with t = u' - 1 < 1 the condition is s > ~20 t.
-// 32 + 128 t is used below u' = 2.  (A constant 1024 made the exact top-1 search of a very dense table impossible: at d = 5,
-// scale 0.01 there are ~10^5 pairs per ulp of u' -- round-3 fuzz.)  Non-decreasing in the bits.
-__host__ __device__ __forceinline__ uint32_t hm_tie_slack(uint32_t ubits)
-{
-    if (ubits >= 0x40000000u) return HM_TIE_SLACK;
-    return 32u + ((ubits > 0x3f800000u ? ubits - 0x3f800000u : 0u) >> 16);
-}
-
 // atomicMax on a word that MANY blocks raise towards the same value (the norm bounds): same-address device-scope atomics
 // serialise at the memory side (~10 ns each: 1 500 of them cost more than the kernel around them), so a wave first reads the
 // word (device scope, fresh) and only sends the atomic when it would raise it -- ~ln(blocks) atomics instead of one per block
@@ -688,7 +696,13 @@ __device__ __forceinline__ uint32_t hm_wave_incl_scan(uint32_t v, int lane)
 // ---- hm_search.hip (host) ----
 int hm_select_sorted(hm_engine* e, uint4* src, uint4* other, uint32_t m, uint32_t k, hipStream_t s);
 void hm_partition_rows(int64_t n, int world, int rank, int64_t* r0, int64_t* r1);      // hm_comm.hip
-int hm_topk_exact(hm_engine* e, float c, float thr, int64_t k, int64_t row_begin, int64_t row_end, int64_t n_limit,
-                  int64_t* n_valid_emitted, int64_t* count, uint4** result_dev, hipStream_t s);      // hm_exact.hip
+// What a top-k search leaves behind: m entries {distance bits | 0xffffffff, i, j, bits(u_c')} in ent (m already clamped to
+// the buffer; ent = nullptr: nothing was searched), `valid` of them below the threshold, and the exact number of candidates
+// in the row range (total = -1: not counted, at least k exist).  The k smallest keys are among the valid entries.
+struct TopkResult { uint4* ent; uint32_t m; int64_t valid; int64_t total; };
+// entries {distance bits, i, j, .} -> the triples of the ABI
+void hm_unpack_entries(const uint4* ent, int64_t n, float* d_out, int32_t* i_out, int32_t* j_out);
+int hm_topk_exact(hm_engine* e, float c, float thr, int64_t k, int64_t row_begin, int64_t row_end, int64_t n_limit, TopkResult* res,
+                  hipStream_t s);      // hm_exact.hip
 int hm_topk_core(hm_engine* e, float c, float thr, int64_t k, int64_t row_begin, int64_t row_end, bool list_all, bool want_count,
-                 int64_t n_limit, int64_t* n_valid_emitted, int64_t* count, uint4** result_dev, hipStream_t s);
+                 int64_t n_limit, TopkResult* res, hipStream_t s);

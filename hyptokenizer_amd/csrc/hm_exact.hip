@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "hm_common.h"
+#include "hm_cut_plan.h"
 #include "hm_rows_device.h"
 
 #pragma clang fp contract(off)
@@ -139,14 +140,12 @@ static int hm_exact_launch(hm_engine* e, ExactArgs& a, hipStream_t s)
     return HM_OK;
 }
 
-// Same contract as hm_topk_core_form (hm_search.hip): entries {distance bits, i, j, bits(u)} in e->ent, their number in
-// *n_valid_emitted and e->h->ctr64[2]; every entry is a candidate (d < thr) and the k smallest keys are among them.
-// *count = the exact number of candidates in the row range.
-int hm_topk_exact(hm_engine* e, float c, float thr, int64_t k, int64_t row_begin, int64_t row_end, int64_t n_limit,
-                  int64_t* n_valid_emitted, int64_t* count, uint4** result_dev, hipStream_t s)
+// Same contract as hm_topk_core_form (hm_search.hip): a TopkResult of entries {distance bits, i, j, bits(u)} in e->ent; every
+// entry is a candidate (d < thr) and the k smallest keys are among them.  total = the exact number of candidates in the row range.
+int hm_topk_exact(hm_engine* e, float c, float thr, int64_t k, int64_t row_begin, int64_t row_end, int64_t n_limit, TopkResult* res,
+                  hipStream_t s)
 {
-    *n_valid_emitted = 0; *count = 0; *result_dev = nullptr;
-    e->h->ctr64[2] = 0;
+    *res = TopkResult{nullptr, 0u, 0, 0};
     const int64_t n = (n_limit >= 0 && n_limit < e->n) ? n_limit : e->n;
     if (row_end < 0 || row_end > n) row_end = n;
     if (row_begin < 0) row_begin = 0;
@@ -161,10 +160,10 @@ int hm_topk_exact(hm_engine* e, float c, float thr, int64_t k, int64_t row_begin
     a.n = (int)n; a.row_begin = (int)row_begin; a.row_end = (int)row_end;
     a.ntj = (int)((n + HM_TILE_ROWS - 1) / HM_TILE_ROWS);
     a.hist = e->d_xhist; a.total = nullptr; a.rowcnt = e->d_rowcnt;
-    a.ent = e->ent; a.emitted = e->d_ctr64 + 2; a.cap = e->ent_cap;
+    a.ent = e->ent; a.emitted = e->d_ctr64 + HM_CTR64_EMITTED; a.cap = e->ent_cap;
     // ---- 1. the k-th smallest distance's bits ----
     static const int kShift[3] = {21, 10, 0}, kBits[3] = {11, 11, 10};
-    uint64_t below = 0, match = 0, total = 0;
+    uint64_t below = 0, match = 0;
     int64_t want = k;
     uint32_t prefix = 0, mask = 0;
     for (int level = 0; level < 3; ++level) {
@@ -172,29 +171,25 @@ int hm_topk_exact(hm_engine* e, float c, float thr, int64_t k, int64_t row_begin
         a.pass = 0; a.prefix = prefix; a.prefix_mask = mask; a.shift = kShift[level]; a.nbits = kBits[level];
         a.total = nullptr;
         if (level == 0) {
-            HM_HIP(hipMemsetAsync(e->d_ctr64, 0, sizeof(unsigned long long), s));
-            a.total = e->d_ctr64;
+            HM_HIP(hipMemsetAsync(e->d_ctr64 + HM_CTR64_SURE, 0, sizeof(unsigned long long), s));
+            a.total = e->d_ctr64 + HM_CTR64_SURE;
         }
         int rc = hm_exact_launch(e, a, s);
         if (rc) return rc;
         HM_HIP(hipMemcpyAsync(e->h->xhist, e->d_xhist, sizeof(unsigned long long) * HM_EXACT_BINS, hipMemcpyDeviceToHost, s));
-        if (level == 0) HM_HIP(hipMemcpyAsync(e->h->ctr64, e->d_ctr64, sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+        if (level == 0)
+            HM_HIP(hipMemcpyAsync(&e->h->ctr64[HM_CTR64_SURE], e->d_ctr64 + HM_CTR64_SURE, sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
         HM_HIP(hipStreamSynchronize(s));
         if (level == 0) {
-            total = e->h->ctr64[0];
-            *count = (int64_t)total;
-            want = std::min<int64_t>(k, (int64_t)total);
+            res->total = (int64_t)e->h->ctr64[HM_CTR64_SURE];
+            want = std::min<int64_t>(k, res->total);
             if (want <= 0) return HM_OK;                      // a pure count, or no candidate
         }
         const uint32_t nb = 1u << kBits[level];
-        uint64_t cum = below;
-        uint32_t dsel = nb - 1;
-        match = 0;
-        for (uint32_t q = 0; q < nb; ++q) {
-            if (cum + e->h->xhist[q] >= (uint64_t)want) { dsel = q; match = e->h->xhist[q]; break; }
-            cum += e->h->xhist[q];
-        }
-        below = cum;
+        const BinHit<uint64_t> hit = hm_first_bin<uint64_t>(e->h->xhist, nb, below, (uint64_t)want);
+        const uint32_t dsel = hit.bin < 0 ? nb - 1 : (uint32_t)hit.bin;
+        below = hit.below;
+        match = hit.in;
         prefix |= dsel << kShift[level];
         mask |= (nb - 1u) << kShift[level];
     }
@@ -219,15 +214,15 @@ int hm_topk_exact(hm_engine* e, float c, float thr, int64_t k, int64_t row_begin
             return hm_fail(e, HM_E_CAPACITY, "exact search: more equal-distance pairs in one row than the emission buffer holds");
     }
     // ---- 3. emission ----
-    HM_HIP(hipMemsetAsync(e->d_ctr64 + 2, 0, sizeof(unsigned long long), s));
+    HM_HIP(hipMemsetAsync(e->d_ctr64 + HM_CTR64_EMITTED, 0, sizeof(unsigned long long), s));
     a.pass = 2;
     int rc = hm_exact_launch(e, a, s);
     if (rc) return rc;
-    HM_HIP(hipMemcpyAsync(&e->h->ctr64[2], e->d_ctr64 + 2, sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+    HM_HIP(hipMemcpyAsync(&e->h->ctr64[HM_CTR64_EMITTED], e->d_ctr64 + HM_CTR64_EMITTED, sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
     HM_HIP(hipStreamSynchronize(s));
-    if (e->h->ctr64[2] > (unsigned long long)e->ent_cap) return hm_fail(e, HM_E_CAPACITY, "exact search: emission count exceeds its own bound");
-    *n_valid_emitted = (int64_t)e->h->ctr64[2];
-    *result_dev = e->ent;
-    e->tm.set_emitted((int64_t)e->h->ctr64[2]);
+    const unsigned long long emitted = e->h->ctr64[HM_CTR64_EMITTED];
+    if (emitted > (unsigned long long)e->ent_cap) return hm_fail(e, HM_E_CAPACITY, "exact search: emission count exceeds its own bound");
+    res->ent = e->ent; res->m = (uint32_t)emitted; res->valid = (int64_t)emitted;
+    e->tm.set_emitted((int64_t)emitted);
     return HM_OK;
 }

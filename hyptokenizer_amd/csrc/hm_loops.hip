@@ -244,10 +244,10 @@ static int hm_issue_segment(hm_engine* e, const StdLoop& L, const BatchSegment& 
     }
     HM_HIP(e->tm.end_segment(s));
     HM_HIP(hipMemcpyAsync(e->h->loop_recs, e->d_loop_recs, sizeof(ArgminRec) * (size_t)seg.count, hipMemcpyDeviceToHost, s));
-    if (piped) HM_HIP(hipMemcpyAsync(&e->h->ctr[7], &e->d_loop->stop, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    if (piped) HM_HIP(hipMemcpyAsync(&e->h->ctr[HM_CTR_LOOP_STOP], &e->d_loop->stop, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
     HM_HIP(hipStreamSynchronize(s));
     hm_unpack_recs(e->h->loop_recs, seg.count, L.rec_out + 4 * seg.first_step, merged);
-    *stop = piped ? e->h->ctr[7] : 0u;
+    *stop = piped ? e->h->ctr[HM_CTR_LOOP_STOP] : 0u;
     return HM_OK;
 }
 

@@ -5,6 +5,7 @@
 // arithmetic from the fp32 image -- a half-wave per entry (coalesced 128-byte row reads,
 // ATen's 32 summation chains one per lane), thresholds compare in fp32, order = (distance bits, i, j).
 #include "hm_common.h"
+#include "hm_cut_plan.h"
 #include "hm_rows_device.h"
 
 #pragma clang fp contract(off)
@@ -181,7 +182,7 @@ int hm_launch_argmin_tail(hm_engine* e, const ScanArgs& sa, float sqrt_c, float 
     t.ent = mf.pipe_ent ? mf.pipe_ent : e->ent; t.ctr64 = mf.pipe_ctr64 ? mf.pipe_ctr64 : e->d_ctr64; t.cap = e->ent_cap;
     t.img = e->img; t.img16 = e->img16; t.RS = e->RS; t.d = e->d; t.KC = e->KC; t.sign_mode = e->sign_mode;
     t.sqrt_c = sqrt_c; t.thr = thr;
-    t.parts = e->d_parts; t.ticket = e->d_ctr + 6;
+    t.parts = e->d_parts; t.ticket = e->d_ctr + HM_CTR_TAIL_TICKET;
     t.out = rec_out; t.out2 = (rec_out == e->d_rec) ? e->d_rec + 1 : nullptr;
     t.seed = with_seed ? e->d_seed : nullptr;
     t.bf = sa.bf16; t.kterms = sa.bf16 ? 8 * e->KC : e->RS; t.rmax2_bits = e->d_rmax2;
@@ -222,8 +223,8 @@ int hm_launch_seed_init(hm_engine* e, const ScanArgs& a, hipStream_t s)
 // top-k: exact distances of the emitted entries
 // ------------------------------------------------------------------------------------------------
 // entries {bits(u_f'), i, j, sure} -> {dbits | 0xffffffff, i, j, bits(u_c')} with the canonical distance.
-// counts[0] valid, counts[1] valid & !sure, counts[3] sure & !valid (margin violated: must be 0),
-// counts[4] valid entries of the COMPLETE region -- the part of the pair space of which every pair was emitted:
+// counts = the engine's counters from HM_CTR_POST_FIRST on: HM_CTR_VALID, HM_CTR_BORDERLINE (valid & !sure), HM_CTR_MARGIN_BAD
+// (sure & !valid, margin violated: must be 0), HM_CTR_COMPLETE = valid entries of the COMPLETE region -- the part of the pair space of which every pair was emitted:
 //   without a row cut: u_c' <= 1 (distance 0) or bits(u_c') + hm_tie_slack(cut_bits) <= cut_bits (a pair with u_c' <= cut
 //   has u_f' <= cut + delta and was emitted; the slack covers the few-ulp wiggle of acosh);
 //   with a row cut (tie flood): the zero-distance pairs of rows i <= tie_imax.
@@ -232,7 +233,7 @@ __global__ __launch_bounds__(256) void hm_post_distance_kernel(uint4* __restrict
                                                                float sqrt_c, float thr, uint32_t cut_bits, int tie_imax,
                                                                uint32_t* __restrict__ counts)
 {
-    const unsigned long long emitted = ctr64[2];
+    const unsigned long long emitted = ctr64[HM_CTR64_EMITTED];
     const uint32_t m = emitted > (unsigned long long)cap ? cap : (uint32_t)emitted;
     const int lane = threadIdx.x & 63;
     uint32_t nv = 0, nb = 0, bad = 0, nc = 0;
@@ -267,10 +268,10 @@ __global__ __launch_bounds__(256) void hm_post_distance_kernel(uint4* __restrict
         nv += __shfl_xor(nv, off, 64); nb += __shfl_xor(nb, off, 64); bad += __shfl_xor(bad, off, 64); nc += __shfl_xor(nc, off, 64);
     }
     if (lane == 0) {
-        if (nv) atomicAdd(&counts[0], nv);
-        if (nb) atomicAdd(&counts[1], nb);
-        if (bad) atomicAdd(&counts[3], bad);
-        if (nc) atomicAdd(&counts[4], nc);
+        if (nv) atomicAdd(&counts[HM_CTR_VALID - HM_CTR_POST_FIRST], nv);
+        if (nb) atomicAdd(&counts[HM_CTR_BORDERLINE - HM_CTR_POST_FIRST], nb);
+        if (bad) atomicAdd(&counts[HM_CTR_MARGIN_BAD - HM_CTR_POST_FIRST], bad);
+        if (nc) atomicAdd(&counts[HM_CTR_COMPLETE - HM_CTR_POST_FIRST], nc);
     }
 }
 
@@ -332,7 +333,7 @@ __global__ void hm_compact_valid_kernel(const uint4* __restrict__ ent, uint32_t 
 // ---- exact order of m unique keys: sorted chunks in LDS, then rank = sum of lower bounds over the chunks ----
 #define HM_SORT_CHUNK 2048
 // bitonic sort of HM_SORT_CHUNK keys per block (padding = all ones), 1024 threads
-__global__ __launch_bounds__(1024) void hm_chunk_sort_kernel(const uint4* __restrict__ ent, uint32_t m, uint4* __restrict__ out)
+__device__ __forceinline__ void hm_chunk_sort_body(const uint4* __restrict__ ent, uint32_t m, uint4* __restrict__ out)
 {
     __shared__ uint4 keys[HM_SORT_CHUNK];
     const uint32_t base = blockIdx.x * HM_SORT_CHUNK;
@@ -357,8 +358,7 @@ __global__ __launch_bounds__(1024) void hm_chunk_sort_kernel(const uint4* __rest
 }
 
 // rank of every key = its index in its own chunk + the lower bounds in all other chunks; rank < k -> out[rank]
-__global__ __launch_bounds__(256) void hm_rank_merge_kernel(const uint4* __restrict__ chunks, uint32_t m, uint32_t nchunks,
-                                                            uint4* __restrict__ out, uint32_t k)
+__device__ __forceinline__ void hm_rank_merge_body(const uint4* __restrict__ chunks, uint32_t nchunks, uint4* __restrict__ out, uint32_t k)
 {
     __shared__ uint4 tile[HM_SORT_CHUNK];
     const uint32_t mine = blockIdx.x * 256 + threadIdx.x;              // position in the chunked array
@@ -383,6 +383,16 @@ __global__ __launch_bounds__(256) void hm_rank_merge_kernel(const uint4* __restr
     if (mine < total && me.y != 0xffffffffu && rank < k) out[rank] = me;
 }
 
+__global__ __launch_bounds__(1024) void hm_chunk_sort_kernel(const uint4* __restrict__ ent, uint32_t m, uint4* __restrict__ out)
+{
+    hm_chunk_sort_body(ent, m, out);
+}
+
+__global__ __launch_bounds__(256) void hm_rank_merge_kernel(const uint4* __restrict__ chunks, uint32_t nchunks, uint4* __restrict__ out, uint32_t k)
+{
+    hm_rank_merge_body(chunks, nchunks, out, k);
+}
+
 // ---- the same two kernels with the entry count taken from device memory (m = min(*m_dev, cap) + m_add): the
 // incremental refresh enqueues its whole chain -- scan, distances, union with the previous list, sort, read-back -- and
 // synchronises once; grids are sized for the most it accepts (HM_RANK_LIMIT entries), surplus blocks leave at once ----
@@ -403,57 +413,17 @@ __global__ __launch_bounds__(256) void hm_append_prev_kernel(uint4* __restrict__
 __global__ __launch_bounds__(1024) void hm_chunk_sort_dev_kernel(const uint4* __restrict__ ent, const unsigned long long* __restrict__ m_dev,
                                                                  uint32_t cap, uint32_t m_add, uint4* __restrict__ out)
 {
-    __shared__ uint4 keys[HM_SORT_CHUNK];
     const uint32_t m = hm_dev_count(m_dev, cap, m_add);
-    const uint32_t base = blockIdx.x * HM_SORT_CHUNK;
-    if (base >= m) return;                                                        // block-uniform
-    for (uint32_t q = threadIdx.x; q < HM_SORT_CHUNK; q += 1024) {
-        const uint32_t idx = base + q;
-        keys[q] = idx < m ? ent[idx] : make_uint4(0xffffffffu, 0xffffffffu, 0xffffffffu, 0);
-    }
-    __syncthreads();
-    for (uint32_t k = 2; k <= HM_SORT_CHUNK; k <<= 1) {
-        for (uint32_t j = k >> 1; j > 0; j >>= 1) {
-            const uint32_t t = threadIdx.x;
-            const uint32_t lo = ((t & ~(j - 1)) << 1) | (t & (j - 1));
-            const uint32_t hi = lo | j;
-            const bool up = (lo & k) == 0;
-            const uint4 x = keys[lo], y = keys[hi];
-            const bool swap = up ? hm_key_less(y.x, y.y, y.z, x.x, x.y, x.z) : hm_key_less(x.x, x.y, x.z, y.x, y.y, y.z);
-            if (swap) { keys[lo] = y; keys[hi] = x; }
-            __syncthreads();
-        }
-    }
-    for (uint32_t q = threadIdx.x; q < HM_SORT_CHUNK; q += 1024) out[base + q] = keys[q];
+    if (blockIdx.x * HM_SORT_CHUNK >= m) return;                                  // block-uniform
+    hm_chunk_sort_body(ent, m, out);
 }
 
 __global__ __launch_bounds__(256) void hm_rank_merge_dev_kernel(const uint4* __restrict__ chunks, const unsigned long long* __restrict__ m_dev,
                                                                 uint32_t cap, uint32_t m_add, uint4* __restrict__ out, uint32_t k)
 {
-    __shared__ uint4 tile[HM_SORT_CHUNK];
-    const uint32_t m = hm_dev_count(m_dev, cap, m_add);
-    const uint32_t nchunks = (m + HM_SORT_CHUNK - 1) / HM_SORT_CHUNK;
-    const uint32_t total = nchunks * HM_SORT_CHUNK;
-    if (blockIdx.x * 256 >= total) return;                                        // block-uniform
-    const uint32_t mine = blockIdx.x * 256 + threadIdx.x;
-    uint4 me = make_uint4(0xffffffffu, 0xffffffffu, 0xffffffffu, 0);
-    if (mine < total) me = chunks[mine];
-    const uint32_t my_chunk = mine / HM_SORT_CHUNK;
-    uint32_t rank = mine % HM_SORT_CHUNK;
-    for (uint32_t c = 0; c < nchunks; ++c) {
-        __syncthreads();
-        for (uint32_t q = threadIdx.x; q < HM_SORT_CHUNK; q += 256) tile[q] = chunks[c * HM_SORT_CHUNK + q];
-        __syncthreads();
-        if (c == my_chunk) continue;
-        uint32_t lo = 0, hi = HM_SORT_CHUNK;
-        while (lo < hi) {
-            const uint32_t mid = (lo + hi) >> 1;
-            const uint4 o = tile[mid];
-            if (hm_key_less(o.x, o.y, o.z, me.x, me.y, me.z)) lo = mid + 1; else hi = mid;
-        }
-        rank += lo;
-    }
-    if (mine < total && me.y != 0xffffffffu && rank < k) out[rank] = me;
+    const uint32_t nchunks = (hm_dev_count(m_dev, cap, m_add) + HM_SORT_CHUNK - 1) / HM_SORT_CHUNK;
+    if (blockIdx.x * 256 >= nchunks * HM_SORT_CHUNK) return;                      // block-uniform
+    hm_rank_merge_body(chunks, nchunks, out, k);
 }
 
 // exact selection of the k smallest keys among m entries of `src` (keys unique; invalid = 0xffffffff)
@@ -482,24 +452,21 @@ int hm_select_sorted(hm_engine* e, uint4* src, uint4* other, uint32_t m, uint32_
             HM_HIP(hipMemcpyAsync(e->h->hist, e->d_hist, sizeof(uint32_t) * HM_DIGIT_BINS, hipMemcpyDeviceToHost, s));
             HM_HIP(hipStreamSynchronize(s));
             const uint32_t nb = 1u << bits;
-            uint32_t cum = below, dsel = nb - 1, match = 0;
-            for (uint32_t q = 0; q < nb; ++q) {
-                if (cum + e->h->hist[q] >= k) { dsel = q; match = e->h->hist[q]; break; }
-                cum += e->h->hist[q];
-            }
-            below = cum;
+            const BinHit<uint32_t> hit = hm_first_bin<uint32_t>(e->h->hist, nb, below, k);
+            const uint32_t dsel = hit.bin < 0 ? nb - 1 : (uint32_t)hit.bin;
+            below = hit.below;
             pf.val[word] |= dsel << shift;
             pf.mask[word] |= ((1u << bits) - 1u) << shift;
-            if (below + match <= rank_limit) break;
+            if (below + hit.in <= rank_limit) break;
         }
-        HM_HIP(hipMemsetAsync(e->d_ctr + 3, 0, sizeof(uint32_t), s));
-        hipLaunchKernelGGL(hm_compact_prefix_kernel, dim3(1024), dim3(256), 0, s, cur, mcur, pf, other, e->d_ctr + 3, e->ent_cap);
+        HM_HIP(hipMemsetAsync(e->d_ctr + HM_CTR_COMPACTED, 0, sizeof(uint32_t), s));
+        hipLaunchKernelGGL(hm_compact_prefix_kernel, dim3(1024), dim3(256), 0, s, cur, mcur, pf, other, e->d_ctr + HM_CTR_COMPACTED, e->ent_cap);
         HM_HIP(hipGetLastError());
-        HM_HIP(hipMemcpyAsync(&e->h->ctr[3], e->d_ctr + 3, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+        HM_HIP(hipMemcpyAsync(&e->h->ctr[HM_CTR_COMPACTED], e->d_ctr + HM_CTR_COMPACTED, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
         HM_HIP(hipStreamSynchronize(s));
         cur = other;
         spare = src;
-        mcur = e->h->ctr[3];
+        mcur = e->h->ctr[HM_CTR_COMPACTED];
         if (mcur > 4u * HM_RANK_LIMIT) return hm_fail(e, HM_E_CAPACITY, "top-k: radix narrowing did not converge");
     }
     // (the scratch holds at least 65536 entries and mcur <= 4 * HM_RANK_LIMIT only when the buffers are 2^24 entries)
@@ -507,7 +474,7 @@ int hm_select_sorted(hm_engine* e, uint4* src, uint4* other, uint32_t m, uint32_
     if ((uint64_t)nchunks * HM_SORT_CHUNK > e->ent_cap) return hm_fail(e, HM_E_CAPACITY, "top-k: sort scratch too small");
     hipLaunchKernelGGL(hm_chunk_sort_kernel, dim3(nchunks), dim3(1024), 0, s, cur, mcur, spare);
     HM_HIP(hipGetLastError());
-    hipLaunchKernelGGL(hm_rank_merge_kernel, dim3(nchunks * (HM_SORT_CHUNK / 256)), dim3(256), 0, s, spare, mcur, nchunks, e->sorted, k);
+    hipLaunchKernelGGL(hm_rank_merge_kernel, dim3(nchunks * (HM_SORT_CHUNK / 256)), dim3(256), 0, s, spare, nchunks, e->sorted, k);
     HM_HIP(hipGetLastError());
     return HM_OK;
 }
@@ -515,206 +482,118 @@ int hm_select_sorted(hm_engine* e, uint4* src, uint4* other, uint32_t m, uint32_
 // Choose an emission cut from sampled histograms of bits(u') so that roughly `target` entries
 // (and certainly not more than the buffer holds) are emitted.  Pure performance heuristic: the
 // caller verifies the outcome (complete-region count) and widens the cut when it was too tight.
+// The passes are issued here; what each histogram means is decided by hm_zoom_decide (hm_cut_plan.h).
 static int hm_estimate_cut(hm_engine* e, ScanArgs a, dim3 grid, int64_t target, uint32_t* cut_bits, int* tie_imax,
                            hipStream_t s)
 {
-    *cut_bits = 0xffffffffu;
-    *tie_imax = 0x7fffffff;
+    *cut_bits = HM_CUT_ALL;
+    *tie_imax = HM_TIE_ALL_ROWS;
     const int64_t pairs = hm_pairs_in_range(a.n, a.row_begin, a.row_end);
     if (pairs <= (int64_t)e->ent_cap / 2) return HM_OK;           // everything fits: emit all candidates
     union { uint32_t u; float f; } hi; hi.f = a.u_hi;
-    uint32_t lo_bits = 0x3f800000u;
-    uint32_t hi_bits = hi.f == INFINITY ? 0x7f800000u : hi.u;
-    int stride = 1;
-    while (stride < 64 && pairs / (stride * 2) > 40000000) stride *= 2;
-    // past C(131 072, 2) pairs: a tie flood puts every sample into one 32-bit bin -- at most ~pairs / stride of them (plus
-    // one tile per row block), so the stride keeps growing until that stays below 2^30
-    while (pairs / stride > ((int64_t)1 << 30)) stride *= 2;
-    double base = 0.0;               // estimated entries below the current zoom window
+    CutWindow w = {HM_CUT_ONE, hi.f == INFINITY ? 0x7f800000u : hi.u, 0.0};
+    const int stride = hm_estimate_stride(pairs);
     for (int zoom = 0; zoom < 6; ++zoom) {
-        uint32_t span = hi_bits - lo_bits;
-        uint32_t shift = 0;
-        while ((span >> shift) > HM_HIST_BINS) ++shift;
-        a.hist_lo = lo_bits;
-        a.hist_shift = shift;
+        a.hist_lo = w.lo_bits;
+        a.hist_shift = hm_zoom_shift(w, HM_HIST_BINS);
         a.sample_stride = stride;
         HM_HIP(hipMemsetAsync(e->d_hist, 0, sizeof(uint32_t) * HM_DIGIT_BINS, s));
         HM_HIP(hm_launch_scan(e, HM_MODE_HIST, a, grid, s));
         HM_HIP(hipMemcpyAsync(e->h->hist, e->d_hist, sizeof(uint32_t) * HM_HIST_BINS, hipMemcpyDeviceToHost, s));
         HM_HIP(hipStreamSynchronize(s));
         e->tm.count_pass();
-        double cum = base;
-        int bsel = -1;
-        for (int q = 0; q < HM_HIST_BINS; ++q) {
-            cum += (double)e->h->hist[q] * stride;
-            if (cum >= (double)target) { bsel = q; break; }
-        }
-        if (bsel < 0) return HM_OK;                                 // fewer than target below u_hi: emit all
-        const double before = cum - (double)e->h->hist[bsel] * stride;
-        const uint32_t edge_lo = lo_bits + ((uint32_t)bsel << shift);
-        const uint32_t edge_hi = lo_bits + (((uint32_t)bsel + 1u) << shift);   // exclusive
-        if (cum <= (double)e->ent_cap * 0.5 || shift == 0) {
-            *cut_bits = edge_hi - 1u;
-            if (cum > (double)e->ent_cap * 0.5) {
-                // a single value of u' holds more entries than the buffer: tie flood.  Emit the tie
-                // value only for the first rows; rows are visited in row-major order by the selection.
-                const double per_row = ((double)e->h->hist[bsel] * stride) / (double)(a.row_end - a.row_begin);
-                double rows = ((double)target - before) / (per_row > 1e-9 ? per_row : 1e-9);
-                // (a slack of 64 rows, fewer where 64 rows of partners would fill more than half the buffer)
-                int64_t pad = 64;
-                while (pad > 1 && pad * (int64_t)a.n > (int64_t)e->ent_cap / 2) pad >>= 1;
-                int64_t imax = a.row_begin + (int64_t)(rows * 2.0) + pad;
-                if (imax > a.row_end) imax = a.row_end;
-                *tie_imax = (int)imax;
-            }
+        const ZoomDecision z = hm_zoom_decide(e->h->hist, HM_HIST_BINS, stride, w, target, e->ent_cap, a.n, a.row_begin, a.row_end);
+        if (z.kind != ZoomDecision::ZOOM) {
+            *cut_bits = z.cut_bits;
+            *tie_imax = z.tie_imax;
             return HM_OK;
         }
-        lo_bits = edge_lo;
-        hi_bits = edge_hi;
-        base = before;
+        w = z.window;
     }
     return HM_OK;
 }
 
+// One prefilter form of the search: the passes CutSearch (hm_cut_plan.h) asks for, until it is done or gives up.
+// res->total: the exact number of candidates, or -1 when want_count is false and at least k exist (not counted)
 static int hm_topk_core_form(hm_engine* e, float c, float thr, int64_t k, int64_t row_begin, int64_t row_end, bool list_all,
-                             bool want_count, int64_t n_limit, int64_t* n_valid_emitted, int64_t* count, uint4** result_dev,
-                             hipStream_t s);
+                             bool want_count, int64_t n_limit, TopkResult* res, hipStream_t s)
+{
+    *res = TopkResult{nullptr, 0u, 0, 0};
+    e->tm.begin_search();
+    const Bounds b = hm_bounds(thr, c);
+    ScanArgs a; dim3 grid;
+    if (b.none || e->n < 2 || !hm_prepare_scan(e, b, row_begin, row_end, a, grid, n_limit)) return HM_OK;
+    const float sqrt_c = sqrtf(c);
+    a.count_sure = (want_count || list_all) ? 1 : 0;
+    CutSearchInput in = {k, list_all, a.count_sure != 0, e->ent_cap, a.row_begin, a.row_end, false, 0u};
+    if (!list_all && k != 0) {
+        const SearchState::Cut& cut = e->st.cut();
+        in.have_cut = a.row_begin == 0 && a.row_end == e->n - 1 && cut.have && cut.k >= k && cut.c == c && cut.bits > HM_CUT_ONE;
+        if (in.have_cut) in.cut_bits = e->st.consume_debug_cut() ? cut.bits : cut.bits + hm_tie_slack(cut.bits);
+    }
+    CutSearch plan(in);
+    PassOutcome o = {};
+    for (;;) {
+        const CutAction act = plan.next();
+        if (act.kind == CutAction::FAIL) return hm_fail(e, act.status, act.message);
+        if (act.kind == CutAction::DONE) break;
+        if (act.kind == CutAction::ESTIMATE) {
+            uint32_t cut_bits; int tie_imax;
+            const int rc = hm_estimate_cut(e, a, grid, act.target, &cut_bits, &tie_imax, s);
+            if (rc) return rc;
+            plan.estimated(cut_bits, tie_imax);
+            continue;
+        }
+        a.cut_bits = act.cut_bits;
+        a.tie_imax = act.tie_imax;
+        HM_HIP(hipMemsetAsync(e->d_ctr, 0, sizeof(uint32_t) * 8, s));
+        HM_HIP(hipMemsetAsync(e->d_ctr64, 0, sizeof(unsigned long long) * 4, s));
+        HM_HIP(hm_launch_scan(e, HM_MODE_TOPK, a, grid, s, e->tm.own().ev0, e->tm.own().ev1));
+        hipLaunchKernelGGL(hm_post_distance_kernel, dim3(1024), dim3(256), 0, s, e->ent, e->d_ctr64, e->ent_cap, e->img, e->RS, e->d,
+                           e->sign_mode, sqrt_c, thr, a.cut_bits, a.tie_imax, e->d_ctr + HM_CTR_POST_FIRST);
+        HM_HIP(hipGetLastError());
+        HM_HIP(hipMemcpyAsync(e->h->ctr, e->d_ctr, sizeof(uint32_t) * 8, hipMemcpyDeviceToHost, s));
+        HM_HIP(hipMemcpyAsync(e->h->ctr64, e->d_ctr64, sizeof(unsigned long long) * 4, hipMemcpyDeviceToHost, s));
+        HM_HIP(hipStreamSynchronize(s));
+        o.emitted = e->h->ctr64[HM_CTR64_EMITTED];
+        o.valid = e->h->ctr[HM_CTR_VALID];
+        o.borderline = e->h->ctr[HM_CTR_BORDERLINE];
+        o.sure = (int64_t)e->h->ctr64[HM_CTR64_SURE];
+        o.complete = e->h->ctr[HM_CTR_COMPLETE];
+        o.margin_violations = e->h->ctr[HM_CTR_MARGIN_BAD];
+        e->tm.add_pass(hm_pairs_in_range(a.n, a.row_begin, a.row_end), (int64_t)o.emitted);
+        plan.scanned(o);
+    }
+    *res = TopkResult{e->ent, (uint32_t)o.emitted, plan.next().valid, plan.next().total};      // (done: the last pass fitted the buffer)
+    return HM_OK;
+}
 
 // The bf16 prefilter's margin (delta ~ 0.004 * max||x_s||^2 in u) makes a shell of undecided pairs around the
 // threshold; every one of them has to be emitted to be decided exactly.  With a threshold inside the bulk of the
 // distance distribution that shell alone can exceed the emission buffer: the search then runs again with the fp32
 // prefilter, whose shell is ~100x thinner.
 int hm_topk_core(hm_engine* e, float c, float thr, int64_t k, int64_t row_begin, int64_t row_end, bool list_all, bool want_count,
-                 int64_t n_limit, int64_t* n_valid_emitted, int64_t* count, uint4** result_dev, hipStream_t s)
+                 int64_t n_limit, TopkResult* res, hipStream_t s)
 {
     const bool had_bf16 = hm_use_bf16(e);
     int rc = HM_E_CAPACITY;
     const bool exact_known = !list_all && (e->force_exact || e->st.straight_to_exact(thr));      // (remembered per table, like the fp32 fallback)
     if (!exact_known && !(had_bf16 && e->st.straight_to_f32(thr)))
-        rc = hm_topk_core_form(e, c, thr, k, row_begin, row_end, list_all, want_count, n_limit, n_valid_emitted, count, result_dev, s);
+        rc = hm_topk_core_form(e, c, thr, k, row_begin, row_end, list_all, want_count, n_limit, res, s);
     if (!exact_known && rc == HM_E_CAPACITY && had_bf16 && !e->force_f32) {
         {
             const HmScopedSet<bool> f32(e->force_f32, true);
-            rc = hm_topk_core_form(e, c, thr, k, row_begin, row_end, list_all, want_count, n_limit, n_valid_emitted, count, result_dev, s);
+            rc = hm_topk_core_form(e, c, thr, k, row_begin, row_end, list_all, want_count, n_limit, res, s);
         }
         if (rc == HM_OK) e->st.remember_f32(thr);
     }
     if (rc == HM_E_CAPACITY && !list_all) {
         // No emission cut fits the buffer in either prefilter form (a table whose distances sit within a few hundred ulps of
         // u = 1): every pair evaluated exactly, selection by counting (hm_exact.hip).  Slow, and always an answer.
-        rc = hm_topk_exact(e, c, thr, k, row_begin, row_end, n_limit, n_valid_emitted, count, result_dev, s);
+        rc = hm_topk_exact(e, c, thr, k, row_begin, row_end, n_limit, res, s);
         if (rc == HM_OK) e->st.remember_exact(thr);
     }
     return rc;
-}
-
-// *count: the exact number of candidates, or -1 when want_count is false and at least k exist (not counted)
-static int hm_topk_core_form(hm_engine* e, float c, float thr, int64_t k, int64_t row_begin, int64_t row_end, bool list_all,
-                             bool want_count, int64_t n_limit, int64_t* n_valid_emitted, int64_t* count, uint4** result_dev,
-                             hipStream_t s)
-{
-    *n_valid_emitted = 0;
-    *count = 0;
-    *result_dev = nullptr;
-    e->tm.begin_search();
-    const Bounds b = hm_bounds(thr, c);
-    ScanArgs a; dim3 grid;
-    if (b.none || e->n < 2 || !hm_prepare_scan(e, b, row_begin, row_end, a, grid, n_limit)) return HM_OK;
-    const float sqrt_c = sqrtf(c);
-    const bool whole = (a.row_begin == 0 && a.row_end == e->n - 1);
-    a.count_sure = (want_count || list_all) ? 1 : 0;
-
-    uint32_t cut_bits = 0xffffffffu;
-    int tie_imax = 0x7fffffff;
-    if (!list_all && k == 0) {
-        cut_bits = 0x3f800000u;          // a pure count: nothing has to be emitted but the undecided shell around the threshold
-        tie_imax = -1;
-    } else if (!list_all) {
-        const SearchState::Cut& cut = e->st.cut();
-        if (whole && cut.have && cut.k >= k && cut.c == c && cut.bits > 0x3f800000u) {
-            cut_bits = e->st.consume_debug_cut() ? cut.bits : cut.bits + hm_tie_slack(cut.bits);
-        } else {
-            int rc = hm_estimate_cut(e, a, grid, 4 * k + 4096, &cut_bits, &tie_imax, s);
-            if (rc) return rc;
-        }
-    }
-    // bracket of the emission cut (bit patterns of u'): the largest cut found too tight (fewer than `want` entries in its
-    // complete region) and the smallest found too generous (emission buffer overflow).  In high dimensions the distances
-    // are so concentrated that P(u - 1 < x) grows like x^(d/2): widening a tight cut geometrically overshoots by orders of
-    // magnitude and a fresh estimate undershoots again -- once both sides are known the cut is bisected between them.
-    uint32_t tight_bits = 0u, loose_bits = 0xffffffffu;
-    int stuck = 0;
-    for (int attempt = 0; attempt < 40; ++attempt) {
-        a.cut_bits = cut_bits;
-        a.tie_imax = tie_imax;
-        HM_HIP(hipMemsetAsync(e->d_ctr, 0, sizeof(uint32_t) * 8, s));
-        HM_HIP(hipMemsetAsync(e->d_ctr64, 0, sizeof(unsigned long long) * 4, s));
-        HM_HIP(hm_launch_scan(e, HM_MODE_TOPK, a, grid, s, e->tm.own().ev0, e->tm.own().ev1));
-        hipLaunchKernelGGL(hm_post_distance_kernel, dim3(1024), dim3(256), 0, s, e->ent, e->d_ctr64, e->ent_cap, e->img, e->RS, e->d,
-                           e->sign_mode, sqrt_c, thr, cut_bits, tie_imax, e->d_ctr + 1);
-        HM_HIP(hipGetLastError());
-        HM_HIP(hipMemcpyAsync(e->h->ctr, e->d_ctr, sizeof(uint32_t) * 8, hipMemcpyDeviceToHost, s));
-        HM_HIP(hipMemcpyAsync(e->h->ctr64, e->d_ctr64, sizeof(unsigned long long) * 4, hipMemcpyDeviceToHost, s));
-        HM_HIP(hipStreamSynchronize(s));
-        e->tm.add_pass(hm_pairs_in_range(a.n, a.row_begin, a.row_end), (int64_t)e->h->ctr64[2]);
-        if (e->h->ctr[4] != 0)
-            return hm_fail(e, HM_E_STATE, "pair scan: prefilter margin violated (an entry classified as surely below the "
-                                          "threshold is not); table holds non-finite rows other than all-NaN rows?");
-        const uint64_t emitted = e->h->ctr64[2];
-        const bool overflow = emitted > e->ent_cap;
-        const int64_t valid = e->h->ctr[1];
-        const int64_t complete = e->h->ctr[5];
-        const bool emitted_all = (cut_bits == 0xffffffffu && tie_imax == 0x7fffffff);
-        if (overflow) {
-            if (list_all) return hm_fail(e, HM_E_CAPACITY, "candidate listing: more candidates than the emission buffer holds");
-            if (tie_imax == 0x7fffffff && tight_bits != 0u) {
-                if (cut_bits < loose_bits) loose_bits = cut_bits;
-                // (a bracket that cannot be split: the shell of undecided pairs around the cut alone overflows the buffer --
-                // the caller retries with the fp32 prefilter, whose shell is ~100x thinner)
-                if (loose_bits <= tight_bits + 1u) return hm_fail(e, HM_E_CAPACITY, "top-k: could not bound the emission");
-                cut_bits = tight_bits + (loose_bits - tight_bits) / 2u;
-                continue;
-            }
-            if (tie_imax == 0x7fffffff && cut_bits < loose_bits) loose_bits = cut_bits;
-            // estimate was too generous (or none was made): estimate with a smaller target
-            const int64_t target = std::max<int64_t>((2 * k + 1024) >> std::min(attempt, 20), k + 64);
-            int rc = hm_estimate_cut(e, a, grid, target, &cut_bits, &tie_imax, s);
-            if (rc) return rc;
-            if (cut_bits == 0xffffffffu) return hm_fail(e, HM_E_CAPACITY, "top-k: could not bound the emission");
-            // the smallest target already, and its cut is one that is known to overflow: estimating again would give the same
-            // cut (a table too dense for any cut of this prefilter form -- the caller moves on to the next form / the exact path)
-            if (tie_imax == 0x7fffffff && target == k + 64 && cut_bits >= loose_bits && ++stuck >= 2)
-                return hm_fail(e, HM_E_CAPACITY, "top-k: could not bound the emission");
-            continue;
-        }
-        // exact total (when counted): sure + valid borderline; everything emitted: the valid ones
-        const int64_t total = emitted_all ? valid : (a.count_sure ? (int64_t)e->h->ctr64[0] + (int64_t)e->h->ctr[2] : -1);
-        const int64_t want = total >= 0 ? std::min<int64_t>(k, total) : k;
-        if (!emitted_all && complete < want) {
-            // fewer than `want` entries lie in the region that is known to be complete: the cut was too tight.
-            // Widen geometrically in the ulp domain (rows for a tie flood) and retry.
-            if (tie_imax != 0x7fffffff) {
-                tie_imax = tie_imax >= a.row_end ? 0x7fffffff : (int)std::min<int64_t>((int64_t)tie_imax * 4 + 256, a.row_end);
-                if (tie_imax >= a.row_end) tie_imax = 0x7fffffff;
-            } else {
-                if (cut_bits > tight_bits) tight_bits = cut_bits;
-                const uint32_t span = cut_bits - 0x3f800000u;
-                const uint64_t nb = (uint64_t)cut_bits + std::max<uint32_t>(span, 4u * hm_tie_slack(cut_bits));
-                if (loose_bits != 0xffffffffu && nb >= (uint64_t)loose_bits) {
-                    if (loose_bits <= tight_bits + 1u) return hm_fail(e, HM_E_CAPACITY, "top-k: could not bound the emission");
-                    cut_bits = tight_bits + (loose_bits - tight_bits) / 2u;
-                } else {
-                    cut_bits = nb >= 0x7f800000ull ? 0xffffffffu : (uint32_t)nb;
-                }
-            }
-            continue;
-        }
-        *count = total;
-        *n_valid_emitted = valid;
-        *result_dev = e->ent;
-        return HM_OK;
-    }
-    return hm_fail(e, HM_E_CAPACITY, "top-k: emission cut did not converge");
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -841,8 +720,7 @@ extern "C" int hm_pairwise_argmin(hm_engine* e, float c, float thr, int64_t row_
 // whole-table search is still the k smallest of the pairs among the rows it saw; the k smallest of the grown table
 // are therefore the k smallest of S[:k] + the pairs that involve a NEW row (j >= prev_n).  Only the last column
 // tile(s) are scanned (cut = largest u' of S[:k], so every new pair that could enter is emitted) and the two lists
-// are merged by the exact selection.  Preconditions checked by the caller; the exact total is not produced here.
-// when the incremental refresh applies (checked by its callers)
+// are merged by the exact selection.  Preconditions checked by the callers (below); the exact total is not produced here.
 static bool hm_topk_incremental_ok(const hm_engine* e, float c, float thr, int64_t k)
 {
     return e->incremental_topk && e->st.incremental_ok(e->n, c, thr, k);
@@ -869,13 +747,13 @@ static int hm_topk_incremental_enqueue(hm_engine* e, float c, float thr, int64_t
         a.tie_imax = 0x7fffffff;
         HM_HIP(hm_launch_scan(e, HM_MODE_TOPK, a, grid, s));
         hipLaunchKernelGGL(hm_post_distance_kernel, dim3(256), dim3(256), 0, s, e->ent, e->d_ctr64, e->ent_cap, e->img, e->RS, e->d,
-                           e->sign_mode, sqrtf(c), thr, a.cut_bits, a.tie_imax, e->d_ctr + 1);
+                           e->sign_mode, sqrtf(c), thr, a.cut_bits, a.tie_imax, e->d_ctr + HM_CTR_POST_FIRST);
         HM_HIP(hipGetLastError());
         e->tm.count_pass();
     }
     // union with the previous list (appended behind the new entries; invalid new entries carry all-ones keys), sorted
     // outright: the count of new entries stays on the device
-    const unsigned long long* m_dev = e->d_ctr64 + 2;
+    const unsigned long long* m_dev = e->d_ctr64 + HM_CTR64_EMITTED;
     const uint32_t room = lim - (uint32_t)k;                                       // new entries the sort can take
     hipLaunchKernelGGL(hm_append_prev_kernel, dim3(64), dim3(256), 0, s, e->ent, m_dev, lim, e->d_prev, (uint32_t)k);
     const uint32_t max_chunks = (lim + HM_SORT_CHUNK - 1) / HM_SORT_CHUNK;
@@ -893,33 +771,29 @@ static int hm_topk_incremental_finish(hm_engine* e, int64_t k, hipStream_t s, ui
 {
     *kk_out = 0;
     HM_HIP(hipStreamSynchronize(s));
-    e->tm.set_emitted((int64_t)e->h->ctr64[2]);
-    if (e->h->ctr64[2] > (unsigned long long)(hm_topk_incremental_limit(e) - (uint32_t)k)) return HM_E_CAPACITY;
+    const unsigned long long emitted = e->h->ctr64[HM_CTR64_EMITTED];          // (the read-back of this chain itself)
+    e->tm.set_emitted((int64_t)emitted);
+    if (emitted > (unsigned long long)(hm_topk_incremental_limit(e) - (uint32_t)k)) return HM_E_CAPACITY;
     *kk_out = (uint32_t)k;
     return HM_OK;
 }
 
-// While rows are only appended, the k smallest keys of the grown table are the k smallest of (the previous
-// list) + (the pairs that involve a NEW row, j >= prev_n): only the last column tiles are scanned (cut = largest u' of
-// the previous list, so every new pair that could enter is emitted) and the union is sorted exactly.
-static int hm_topk_incremental(hm_engine* e, float c, float thr, int64_t k, hipStream_t s, uint32_t* kk_out)
+// entries {distance bits, i, j, .} -> the triples of the ABI
+void hm_unpack_entries(const uint4* ent, int64_t n, float* d_out, int32_t* i_out, int32_t* j_out)
 {
-    *kk_out = 0;
-    const int rc = hm_topk_incremental_enqueue(e, c, thr, k, s);
-    if (rc) return rc;
-    return hm_topk_incremental_finish(e, k, s, kk_out);
+    for (int64_t t = 0; t < n; ++t) {
+        union { uint32_t u; float f; } cv; cv.u = ent[t].x;
+        d_out[t] = cv.f; i_out[t] = (int32_t)ent[t].y; j_out[t] = (int32_t)ent[t].z;
+    }
 }
 
 // host side of a finished top-k search whose ordered list sits in e->h_sorted: outputs and the state the next refresh uses
 static void hm_topk_publish(hm_engine* e, uint32_t kk, int64_t k, float c, float thr, bool keep, float* d_out, int32_t* i_out, int32_t* j_out,
                             int64_t* n_out)
 {
+    hm_unpack_entries(e->h_sorted, kk, d_out, i_out, j_out);
     uint32_t mx = 0;
-    for (uint32_t t = 0; t < kk; ++t) {
-        union { uint32_t u; float f; } cv; cv.u = e->h_sorted[t].x;
-        d_out[t] = cv.f; i_out[t] = (int32_t)e->h_sorted[t].y; j_out[t] = (int32_t)e->h_sorted[t].z;
-        mx = std::max(mx, e->h_sorted[t].w);     // entries are ordered by distance, not by u': the max u' bits of the selection
-    }
+    for (uint32_t t = 0; t < kk; ++t) mx = std::max(mx, e->h_sorted[t].w);     // entries are ordered by distance, not by u': the max u' bits of the selection
     *n_out = kk;
     // remember the largest u' of the selection: while rows are only appended, the k-th smallest key can
     // only move down, so this cut (+ tie slack) is a guaranteed superset for the next refresh
@@ -943,22 +817,21 @@ static int hm_topk_impl(hm_engine* e, float c, float thr, int64_t k, int64_t row
     uint32_t kk = 0;
     bool done = false;
     if (!want_count && whole && hm_topk_incremental_ok(e, c, thr, k)) {
-        const int rc = hm_topk_incremental(e, c, thr, k, s, &kk);
+        int rc = hm_topk_incremental_enqueue(e, c, thr, k, s);
+        if (rc == HM_OK) rc = hm_topk_incremental_finish(e, k, s, &kk);
         if (rc == HM_OK) { done = true; *count = -1; }
         else if (rc != HM_E_CAPACITY) return rc;
     }
     if (!done) {
-        int64_t valid = 0, total = 0;
-        uint4* res = nullptr;
-        int rc = hm_topk_core(e, c, thr, k, row_begin, row_end, false, want_count || k == 0, -1, &valid, &total, &res, s);
+        TopkResult res;
+        int rc = hm_topk_core(e, c, thr, k, row_begin, row_end, false, want_count || k == 0, -1, &res, s);
         if (rc) return rc;
         // the uncounted form answers -1 once k candidates exist (include/hypmerge.h), also where a small table's search
         // emitted every candidate and so knows their number
-        *count = (!want_count && k > 0 && total >= k) ? -1 : total;
-        kk = (uint32_t)std::min<int64_t>(k, valid);
-        if (kk == 0 || !res) { e->st.drop_prev(); return HM_OK; }
-        const uint32_t m = (uint32_t)std::min<uint64_t>(e->h->ctr64[2], e->ent_cap);
-        rc = hm_select_sorted(e, res, e->ent2, m, kk, s);
+        *count = (!want_count && k > 0 && res.total >= k) ? -1 : res.total;
+        kk = (uint32_t)std::min<int64_t>(k, res.valid);
+        if (kk == 0 || !res.ent) { e->st.drop_prev(); return HM_OK; }
+        rc = hm_select_sorted(e, res.ent, e->ent2, res.m, kk, s);
         if (rc) return rc;
     }
     const bool keep = (kk == k && whole);
@@ -1024,32 +897,27 @@ extern "C" int hm_pairwise_count(hm_engine* e, float c, float thr, int64_t n_lim
     e->st.disarm();
     HM_HIP(hipSetDevice(e->device));
     *count = 0;
-    int64_t valid = 0, total = 0;
-    uint4* res = nullptr;
+    TopkResult res;
     const SearchState::Cut cut = e->st.suspend_cut();     // a count does not disturb the cut prediction of the refreshes
-    int rc = hm_topk_core(e, c, thr, 0, 0, -1, false, true, n_limit, &valid, &total, &res, (hipStream_t)stream);
+    int rc = hm_topk_core(e, c, thr, 0, 0, -1, false, true, n_limit, &res, (hipStream_t)stream);
     e->st.restore_cut(cut);
     if (rc) return rc;
-    *count = total;
+    *count = res.total;
     return HM_OK;
 }
 
-// valid entries of the listing in e->ent (m emitted) -> host triples out[0, min(valid, room))
-static int hm_copy_valid(hm_engine* e, const uint4* res, int64_t valid, int64_t room, int32_t* i_out, int32_t* j_out, float* d_out,
+// valid entries of a listing -> host triples out[0, min(valid, room))
+static int hm_copy_valid(hm_engine* e, const TopkResult& res, int64_t room, int32_t* i_out, int32_t* j_out, float* d_out,
                          int64_t* ncopy, hipStream_t s)
 {
-    const uint32_t m = (uint32_t)std::min<uint64_t>(e->h->ctr64[2], e->ent_cap);
-    HM_HIP(hipMemsetAsync(e->d_ctr + 3, 0, sizeof(uint32_t), s));
-    hipLaunchKernelGGL(hm_compact_valid_kernel, dim3(1024), dim3(256), 0, s, res, m, e->ent2, e->d_ctr + 3, e->ent_cap);
+    HM_HIP(hipMemsetAsync(e->d_ctr + HM_CTR_COMPACTED, 0, sizeof(uint32_t), s));
+    hipLaunchKernelGGL(hm_compact_valid_kernel, dim3(1024), dim3(256), 0, s, res.ent, res.m, e->ent2, e->d_ctr + HM_CTR_COMPACTED, e->ent_cap);
     HM_HIP(hipGetLastError());
-    *ncopy = std::min<int64_t>(valid, room);
+    *ncopy = std::min<int64_t>(res.valid, room);
     std::vector<uint4> host((size_t)*ncopy);
     HM_HIP(hipMemcpyAsync(host.data(), e->ent2, sizeof(uint4) * (size_t)*ncopy, hipMemcpyDeviceToHost, s));
     HM_HIP(hipStreamSynchronize(s));
-    for (int64_t t = 0; t < *ncopy; ++t) {
-        union { uint32_t u; float f; } cv; cv.u = host[(size_t)t].x;
-        d_out[t] = cv.f; i_out[t] = (int32_t)host[(size_t)t].y; j_out[t] = (int32_t)host[(size_t)t].z;
-    }
+    hm_unpack_entries(host.data(), *ncopy, d_out, i_out, j_out);
     return HM_OK;
 }
 
@@ -1061,12 +929,11 @@ static int hm_candidates_by_rows(hm_engine* e, float c, float thr, int64_t row_b
 {
     const int64_t n = e->n;
     const int64_t r0 = std::max<int64_t>(row_begin, 0), r1 = (row_end < 0 || row_end > n - 1) ? n - 1 : row_end;
-    int64_t valid = 0, cnt = 0;
-    uint4* res = nullptr;
-    int rc = hm_topk_core(e, c, thr, 0, r0, r1, false, true, -1, &valid, &cnt, &res, s);
+    TopkResult res;
+    int rc = hm_topk_core(e, c, thr, 0, r0, r1, false, true, -1, &res, s);
     if (rc) return rc;
-    *total = cnt;
-    const int64_t want = std::min<int64_t>(cap, cnt);
+    *total = res.total;
+    const int64_t want = std::min<int64_t>(cap, res.total);
     int64_t got = 0;
     for (int64_t lo = r0; lo < r1 && got < want;) {
         int64_t hi = lo + 1, step = 1;
@@ -1074,11 +941,11 @@ static int hm_candidates_by_rows(hm_engine* e, float c, float thr, int64_t row_b
             if (hi + step <= r1 && hm_pairs_in_range(n, lo, hi + step) <= (int64_t)e->ent_cap) { hi += step; step *= 2; }
             else step /= 2;
         }
-        rc = hm_topk_core(e, c, thr, 0, lo, hi, true, true, -1, &valid, &cnt, &res, s);
+        rc = hm_topk_core(e, c, thr, 0, lo, hi, true, true, -1, &res, s);
         if (rc) return rc;
-        if (res && valid > 0) {
+        if (res.ent && res.valid > 0) {
             int64_t ncopy = 0;
-            rc = hm_copy_valid(e, res, valid, want - got, i_out + got, j_out + got, d_out + got, &ncopy, s);
+            rc = hm_copy_valid(e, res, want - got, i_out + got, j_out + got, d_out + got, &ncopy, s);
             if (rc) return rc;
             got += ncopy;
         }
@@ -1099,15 +966,14 @@ extern "C" int hm_pairwise_candidates(hm_engine* e, float c, float thr, int64_t 
     hipStream_t s = (hipStream_t)stream;
     HM_HIP(hipSetDevice(e->device));
     *total = 0;
-    int64_t valid = 0, cnt = 0;
-    uint4* res = nullptr;
-    int rc = hm_topk_core(e, c, thr, 0, row_begin, row_end, true, true, -1, &valid, &cnt, &res, s);
+    TopkResult res;
+    int rc = hm_topk_core(e, c, thr, 0, row_begin, row_end, true, true, -1, &res, s);
     if (rc == HM_E_CAPACITY) return hm_candidates_by_rows(e, c, thr, row_begin, row_end, cap, i_out, j_out, d_out, total, s);
     if (rc) return rc;
-    *total = cnt;
-    if (!res || valid == 0 || cap == 0) return HM_OK;
+    *total = res.total;
+    if (!res.ent || res.valid == 0 || cap == 0) return HM_OK;
     int64_t ncopy = 0;
-    return hm_copy_valid(e, res, valid, cap, i_out, j_out, d_out, &ncopy, s);
+    return hm_copy_valid(e, res, cap, i_out, j_out, d_out, &ncopy, s);
 }
 
 extern "C" int hm_row_argmin(hm_engine* e, int64_t row, int64_t n_partners, float c, float thr, float* d, int32_t* i, int32_t* j,
@@ -1127,9 +993,9 @@ extern "C" int hm_row_argmin(hm_engine* e, int64_t row, int64_t n_partners, floa
     HM_HIP(hipMemsetAsync(key, 0xff, sizeof(unsigned long long), s));
     int rc = hm_launch_row_key(e, row, n_partners, sqrtf(c), thr, key, s);
     if (rc) return rc;
-    HM_HIP(hipMemcpyAsync(&e->h->ctr64[3], key, sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+    HM_HIP(hipMemcpyAsync(&e->h->ctr64[HM_CTR64_ROW_KEY], key, sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
     HM_HIP(hipStreamSynchronize(s));
-    const unsigned long long k64 = e->h->ctr64[3];
+    const unsigned long long k64 = e->h->ctr64[HM_CTR64_ROW_KEY];
     if (k64 != ~0ull) {
         union { uint32_t u; float f; } cv; cv.u = (uint32_t)(k64 >> 32);
         const int64_t p = (int64_t)(uint32_t)k64;

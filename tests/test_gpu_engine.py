@@ -474,6 +474,37 @@ def test_forced_tight_cut_is_detected(oracle):
     assert np.array_equal(gi, oi) and np.array_equal(gj, oj) and np.array_equal(_bits(gd), _bits(od))
 
 
+@pytest.mark.parametrize("n", [64, 65, 91, 92])
+def test_selection_at_the_edges_of_a_sort_chunk(oracle, n):
+    """Every pair of the table selected and ordered: 2 016 / 2 080 and 4 095 / 4 186 entries, either side of one and of two
+    sort chunks of 2 048 (hm_chunk_sort_kernel / hm_rank_merge_kernel); on the 64-row table also through the pair of kernels
+    that take their count from the device -- the incremental refresh of the table grown by one row sorts the 2 016 entries of
+    the previous list plus those of the new row, across a chunk edge."""
+    d, thr = 10, 30.0                                      # a threshold above every distance of the table
+    X = lorentz_table(n, d, seed=42, scale=0.05)
+    eng, table = _engine(X, "lorentz", n + 8)
+    k = n * (n - 1) // 2
+    od, oi, oj, oc = oracle.pairwise_topk(X.numpy(), n, 1.0, thr, 1, k)
+    assert oc == k and len(od) == k and float(od.max()) < thr
+    gd, gi, gj, gc = eng.topk(1.0, thr, k)
+    assert gc == oc and np.array_equal(gi, oi) and np.array_equal(gj, oj) and np.array_equal(_bits(gd), _bits(od))
+    if n != 64:
+        return
+    eng.merge_append(int(oi[0]), int(oj[0]), 0.5, 1.0, table, n)
+    od, oi, oj, oc = oracle.pairwise_topk(table.cpu().numpy(), n + 1, 1.0, thr, 1, k)
+    gd, gi, gj, gc = eng.topk(1.0, thr, k, count=False)
+    assert gc == -1 and np.array_equal(gi, oi) and np.array_equal(gj, oj) and np.array_equal(_bits(gd), _bits(od))
+    # the incremental route: one untimed pass over the new row's column tile -- a full search reports the pairs it scanned
+    st = eng.scan_stats()
+    assert st["passes"] == 1 and st["pairs"] == 0 and 0 < st["emitted"] <= n, st
+    # ... and asked for as engine_walk.py asks: the refresh in two halves is accepted and delivers a list
+    eng.merge_append(int(oi[1]), int(oj[1]), 0.5, 1.0, table, n + 1)
+    assert eng.topk_refresh_begin(1.0, thr, k)
+    r = eng.topk_refresh_end()
+    od, oi, oj, oc = oracle.pairwise_topk(table.cpu().numpy(), n + 2, 1.0, thr, 1, k)
+    assert r is not None and np.array_equal(r[1], oi) and np.array_equal(r[2], oj) and np.array_equal(_bits(r[0]), _bits(od))
+
+
 @pytest.mark.parametrize("mode", ["lorentz", "reference"])
 def test_golden_candidate_lists_on_the_hip_engine(golden_dir, mode):
     """G2 (reference's own _find_merge_candidates / _find_merge_candidates_fast lists) fed to the HIP engine
