@@ -6,6 +6,8 @@
 //   hm_batch_plan.h the standard loop's redo policy: which steps are issued next, in which form (host, no HIP)
 //   hm_cut_plan.h   the top-k search's emission cut: which pass comes next, with which cut (host, no HIP)
 //   hm_tie_slack.h  hm_tie_slack, the one function the kernels and hm_cut_plan.h share
+//   hm_scan_geom.h  the pair scan's geometry: constants of a kernel instantiation, LDS map, block shapes, instantiated widths (no HIP)
+//   hm_scan_plan.h  the pair scan's host policy and item list: encode and decode (no HIP)
 //   hm_scan.hip     the pair-scan kernel (MFMA prefilter) and its launch  (hot kernel)
 //   hm_search.hip   exact re-evaluation / selection kernels and the search entry points of the ABI
 //   hm_rows.hip     the engine's row work: image construction, merge / midpoint, one-row-vs-all and gathered distances
@@ -50,6 +52,7 @@
 
 #include "../../include/hypmerge.h"
 #include "hm_device_math.h"
+#include "hm_scan_plan.h"
 #include "hm_state.h"
 #include "hm_tie_slack.h"
 
@@ -61,12 +64,8 @@ typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 // ------------------------------------------------------------------------------------------------
 // constants
 // ------------------------------------------------------------------------------------------------
-#define HM_MAX_BLOCK_ROWS 1024
+// (HM_MAX_BLOCK_ROWS, HM_MODE_*, HM_HIST_BINS: hm_scan_geom.h)
 #define HM_MAX_D1 132              // largest table width (d + 1 <= 129) rounded up
-#define HM_MODE_TOPK 0
-#define HM_MODE_ARGMIN 1
-#define HM_MODE_HIST 2
-#define HM_HIST_BINS 256
 #define HM_DIGIT_BINS 4096
 #define HM_EXACT_BINS 2048            // hm_exact.hip: bins of one digit of the distance bits (11 + 11 + 10)
 #define HM_RANK_LIMIT 49152        // rank sort is O(M^2): narrow by radix digits above this
@@ -87,10 +86,7 @@ typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 #define HM_PREFILTER_F32 1
 #define HM_PREFILTER_BF16 2
 
-// floats per fp32 image row
-__host__ __device__ constexpr int hm_row_floats(int NG) { return 4 * NG + 4 + (((NG + 1) % 2 == 0) ? 4 : 0); }
-// 16-byte chunks per bf16 image row: KC chunks of 8 K-slots (+ the [x0] chunk that makes an even count odd)
-__host__ __device__ constexpr int hm_row16_chunks(int KC) { return KC + ((KC & 1) ? 0 : 1); }
+// (hm_row_floats, hm_row16_chunks -- floats per fp32 image row, 16-byte chunks per bf16 image row: hm_scan_geom.h)
 __device__ __forceinline__ int hm_pos_in_group(int s) { return ((s & 1) << 1) | ((s >> 1) & 1); }  // 0,2,1,3
 // offset of spatial coordinate s inside an fp32 image row
 __device__ __forceinline__ int hm_img_off(int s) { return 4 * (s >> 2) + hm_pos_in_group(s & 3); }
@@ -117,20 +113,13 @@ struct ScanArgs {
     const float* img;
     const unsigned char* img16;   // bf16 image (BF = 1 kernels)
     int bf16;                     // host-side: which form this launch uses
-    int shape;                    // host-side: block shape selector of the bf16 form (0: 256-row blocks, 1: 512-row blocks)
+    int shape;                    // host-side: block shape of this launch (kScanShapes, hm_scan_geom.h)
     int n;                        // live rows
     int row_begin, row_end;       // i range
     int col_begin;                // only pairs with j >= col_begin (incremental refresh: the rows appended since the last one)
     int rb_first;                 // first row block
     int nct;                      // column tiles in total = ceil(n / cols per tile)
-    // work decomposition: 1-D grid of items in up to HM_SCAN_PHASES phases.  Phase q covers the row blocks from ph_rb0[q]
-    // up to the next phase's first; each of its ph_items[q] blocks takes ph_ch[q] column tiles (item b of the phase: row block
-    // ph_rb0[q] + b / ph_chunks[q], tiles from ph_ctmin[q] + (b % ph_chunks[q]) * ph_ch[q]).  Chunk lengths shrink from
-    // phase to phase: long items first, ever shorter ones behind them, so that the slots that free up late are filled
-    // with work that still ends with the rest (the launch's tail is made of the shortest blocks).
-#define HM_SCAN_PHASES 6
-    int n_ph;
-    int ph_items[HM_SCAN_PHASES], ph_rb0[HM_SCAN_PHASES], ph_chunks[HM_SCAN_PHASES], ph_ch[HM_SCAN_PHASES], ph_ctmin[HM_SCAN_PHASES];
+    ScanItems items;              // work decomposition: the list the blocks walk (hm_scan_plan.h; decoded by HM_SCAN_ITEM_DECODE only)
     float u_hi;                   // candidate prefilter: u < u_hi
     float u_lo;                   // surely-below-threshold bound: u' < u_lo
     uint32_t cut_bits;            // emit when bits(u') <= cut_bits (or not sure)
@@ -231,21 +220,12 @@ struct LoopState {
 struct hm_engine {
     int device = 0;
     int n_cu = 256;
-    // work-decomposition knobs (hm_debug_set_knob; tuning builds also read HM_TUNE_<NAME>)
-    int chunk_f32 = 32, chunk_bf16 = 128, tail_div = 4;   // (bf16: 96 with the static grid; 112-144 measure alike with the item queue)
-    double tail_fraction = 0.20;
-    // phases of the item list: work share of each phase from the top of the triangle (the last one takes the rest), chunk
-    // length divisor per phase.  phases = 2 is the round-2 list: [1 - tail_fraction, tail_fraction] at [1, tail_div]
-    int phases = 4;                      // (measured, interleaved A/B at V = 50 k / 100 k: +1.3 % / +2.6 % over the two-phase list)
-    double ph_share[HM_SCAN_PHASES - 1] = {0.70, 0.15, 0.10, 0.0, 0.0};
-    int ph_div[HM_SCAN_PHASES] = {1, 2, 4, 8, 16, 32};
+    ScanPlanKnobs plan;                   // work-decomposition knobs of the scan (hm_scan_plan.h)
     unsigned long long* d_queue = nullptr; // item queue words: 2 x 128 B (one per counter set), never reset (ScanArgs::q_tag)
     int dyn_slots = 0;                    // knob `dyn_slots` (tests): resident-grid size of the item queue; 0 = what the device holds (occupancy x CUs)
     bool dyn_queue = true;                // knob `dyn`: resident grid + in-order item queue (ScanArgs::dyn) for ARGMIN / TOPK launches
     unsigned long long scan_tag = 0;      // launch tags of the item queue (monotonic per engine)
     std::map<const void*, int> scan_slots; // resident blocks per scan kernel instantiation on this engine's device
-    int force_shape = -1;                 // HM_TUNE_SHAPE: bf16 block shape of every launch (tuning builds)
-    int64_t big_min_rows = 80000;         // bf16 form: launches covering at least the pairs of this many rows use 512-row blocks
     int head = HM_SCAN_HEAD;              // knob `head`: k-steps of the argmin scan's head test (hm_head_steps); 0 = the kernels without it
     bool head_force = false;              // knob `head_force` (tests): every eligible argmin launch takes the head kernel, whatever hm_head_live expects
     int64_t head_merges = 0;              // merged rows appended since the table was set or an existing row changed (hm_head_live)
@@ -389,7 +369,7 @@ bool hm_prepare_scan(hm_engine* e, const Bounds& b, int64_t row_begin, int64_t r
                      int64_t col_begin = 0);
 hipError_t hm_launch_scan(hm_engine* e, int mode, const ScanArgs& a, dim3 grid, hipStream_t s, hipEvent_t ev0 = nullptr,
                           hipEvent_t ev1 = nullptr);
-int64_t hm_pairs_in_range(int64_t n, int64_t r0, int64_t r1);
+// (hm_pairs_in_range: hm_scan_plan.h)
 
 // ---- hm_rows.hip ----
 int hm_build_rows(hm_engine* e, const float* X, int64_t ld, int64_t r0, int64_t r1, hipStream_t s);

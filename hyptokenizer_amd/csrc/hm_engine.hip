@@ -17,8 +17,11 @@ int hm_fail(hm_engine* e, int code, const std::string& msg)
     return code;
 }
 
-static const int kSupportedNG[] = {1, 2, 3, 4, 6, 8, 10, 13, 16, 20, 25, 28, 32};
-static const int kSupportedKC[] = {2, 4, 8, 13, 14, 16};   // bf16 form: chunks of 8 K-slots (two per k-step; 13 ends on a half step)
+// the widths the scan kernels are instantiated for (hm_scan_geom.h: the list hm_launch_scan switches over), ascending
+#define HM_WIDTH(v) v,
+static const int kSupportedNG[] = {HM_SCAN_NG_LIST(HM_WIDTH, HM_SCAN_WIDTHS_ALL)};
+static const int kSupportedKC[] = {HM_SCAN_KC_LIST(HM_WIDTH, HM_SCAN_WIDTHS_ALL)};
+#undef HM_WIDTH
 
 static int hm_pick_kc(int d)
 {
@@ -48,15 +51,15 @@ static std::map<std::string, double> g_default_knobs;          // applied to eve
 static int hm_apply_knob(hm_engine* e, const char* name, double v)
 {
     const std::string k = name ? name : "";
-    if (k == "chunk") { if (!(v >= 4 && v <= 4096)) return HM_E_ARG; e->chunk_f32 = e->chunk_bf16 = (int)v; }
-    else if (k == "tail") { if (!(v >= 0.0 && v <= 0.9)) return HM_E_ARG; e->tail_fraction = v; }
-    else if (k == "tail_div") { if (!(v >= 1 && v <= 16)) return HM_E_ARG; e->tail_div = (int)v; }
-    else if (k == "big_rows") { if (!(v >= 0)) return HM_E_ARG; e->big_min_rows = (int64_t)v; }          // 512-row blocks from this many rows' pairs on
-    else if (k == "shape") { if (!(v >= -1 && v <= 4)) return HM_E_ARG; e->force_shape = (int)v; }
+    if (k == "chunk") { if (!(v >= 4 && v <= 4096)) return HM_E_ARG; e->plan.chunk_f32 = e->plan.chunk_bf16 = (int)v; }
+    else if (k == "tail") { if (!(v >= 0.0 && v <= 0.9)) return HM_E_ARG; e->plan.tail_fraction = v; }
+    else if (k == "tail_div") { if (!(v >= 1 && v <= 16)) return HM_E_ARG; e->plan.tail_div = (int)v; }
+    else if (k == "big_rows") { if (!(v >= 0)) return HM_E_ARG; e->plan.big_min_rows = (int64_t)v; }          // 512-row blocks from this many rows' pairs on
+    else if (k == "shape") { if (!(v >= -1 && v <= 4)) return HM_E_ARG; e->plan.force_shape = (int)v; }
     else if (k == "incr_topk") e->incremental_topk = v != 0.0;
-    else if (k == "phases") { if (!(v >= 1 && v <= HM_SCAN_PHASES)) return HM_E_ARG; e->phases = (int)v; }
-    else if (k.size() == 9 && k.compare(0, 8, "ph_share") == 0 && k[8] >= '0' && k[8] < '0' + HM_SCAN_PHASES - 1) { if (!(v >= 0.0 && v <= 1.0)) return HM_E_ARG; e->ph_share[k[8] - '0'] = v; }
-    else if (k.size() == 7 && k.compare(0, 6, "ph_div") == 0 && k[6] >= '1' && k[6] < '0' + HM_SCAN_PHASES) { if (!(v >= 1 && v <= 64)) return HM_E_ARG; e->ph_div[k[6] - '0'] = (int)v; }
+    else if (k == "phases") { if (!(v >= 1 && v <= HM_SCAN_PHASES)) return HM_E_ARG; e->plan.phases = (int)v; }
+    else if (k.size() == 9 && k.compare(0, 8, "ph_share") == 0 && k[8] >= '0' && k[8] < '0' + HM_SCAN_PHASES - 1) { if (!(v >= 0.0 && v <= 1.0)) return HM_E_ARG; e->plan.ph_share[k[8] - '0'] = v; }
+    else if (k.size() == 7 && k.compare(0, 6, "ph_div") == 0 && k[6] >= '1' && k[6] < '0' + HM_SCAN_PHASES) { if (!(v >= 1 && v <= 64)) return HM_E_ARG; e->plan.ph_div[k[6] - '0'] = (int)v; }
     else if (k == "dyn_slots") { if (!(v >= 0 && v <= 65536)) return HM_E_ARG; e->dyn_slots = (int)v; }
     else if (k == "head") { if (!(v == 0.0 || v == (double)HM_SCAN_HEAD)) return HM_E_ARG; e->head = (int)v; }      // argmin scan, bf16 form: 0 = no head test
     else if (k == "head_force") e->head_force = v != 0.0;
@@ -328,13 +331,6 @@ Bounds hm_bounds(float thr, float c)
         b.u_lo = f < 1.0f ? 1.0f : f;
     }
     return b;
-}
-
-int64_t hm_pairs_in_range(int64_t n, int64_t r0, int64_t r1)
-{
-    // sum_{i=r0}^{r1-1} (n - 1 - i)
-    const int64_t cnt = r1 - r0;
-    return cnt * (n - 1) - (r0 + r1 - 1) * cnt / 2;
 }
 
 extern "C" int hm_last_scan_stats(const hm_engine* e, float* scan_ms, int64_t* pairs, int64_t* emitted, int32_t* passes)

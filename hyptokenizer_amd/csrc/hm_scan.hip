@@ -23,21 +23,7 @@
 
 #pragma clang fp contract(off)
 
-#ifndef HM_SUB_BF16
-#define HM_SUB_BF16 4              // bf16 form: 32-column groups per streamed tile (128 partner rows per barrier)
-#endif
-#ifndef HM_SUB_F32
-#define HM_SUB_F32 2
-#endif
-#ifndef HM_DIST_BF16
-#define HM_DIST_BF16 1             // tiles in flight ahead of the computed one (ring of DIST + 1 slots)
-#endif
-#ifndef HM_WPB_BIG
-#define HM_WPB_BIG 8               // bf16 form, large launches: 8 waves x 64 rows = 512-row blocks (half the L2 -> LDS fill traffic)
-#endif
-#ifndef HM_SCAN_INSTANTIATE_ALL
-#define HM_SCAN_INSTANTIATE_ALL 1  // 0: only d = 100 (13 chunks / NG = 25) -- quick builds for tuning runs
-#endif
+// (HM_SUB_BF16, HM_SUB_F32, HM_DIST_BF16, HM_SCAN_INSTANTIATE_ALL, HM_SCAN_ALL_SHAPES: hm_scan_geom.h)
 
 // CNT (1..4) consecutive 1 KiB LDS-DMA pieces in one statement: one M0 write; the immediate offset of
 // global_load_lds applies to the global and to the LDS address alike, so the pieces share both bases.
@@ -105,27 +91,16 @@ __global__ __launch_bounds__(64 * WPB, 2) void hm_scan_kernel(const ScanArgs p)
 {
     static_assert(SUB % 2 == 0, "the two accumulator sets alternate between column groups: an even number per tile");
     constexpr bool PIPE = (TM <= HM_SCAN_PIPE_MAX_TM);   // two accumulator sets fit the registers (128 stationary rows per wave: one set)
-    constexpr int COLS = 32 * SUB;                 // partner rows per streamed tile
-    constexpr int RS = hm_row_floats(NG);          // fp32 image: floats per row
-    constexpr int RB16 = 16 * hm_row16_chunks(NG); // bf16 image: bytes per row (NG chunks of 8 bf16 [+ the [x0 fp32] chunk])
+    // the geometry of this instantiation (hm_scan_geom.h: sizes, ring, LDS map)
+    using G = ScanGeom<NG, BF, TM, WPB, SUB>;
+    constexpr int COLS = G::COLS, RS = G::RS, RB16 = G::RB16, TILE_BYTES = G::TILE_BYTES, NP = G::NP;
+    constexpr int PPW = G::PPW, TILE_LDS = G::TILE_LDS, DIST = G::DIST, NBUF = G::NBUF;
+    constexpr int WAVE_ROWS = G::WAVE_ROWS, BLOCK_ROWS = G::BLOCK_ROWS, NTHREADS = G::NTHREADS;
     constexpr bool HALF_LAST = (BF != 0) && (NG & 1);   // the last k-step covers one chunk only (8 K-slots)
-    constexpr int ROW_BYTES = BF ? RB16 : RS * 4;
-    constexpr int TILE_BYTES = COLS * ROW_BYTES;
-    constexpr int NP = BF ? (NG + 1) / 2 : NG + 1; // k-steps: fp32: NG spatial groups + time; bf16: two chunks per step
-    constexpr int NPIECE = TILE_BYTES / 1024;      // 1 KiB pieces per tile
     constexpr int TCH = RS / 4 - 1;                // fp32 image: chunk index of the time group
-    constexpr int PPW = (NPIECE + WPB - 1) / WPB;  // LDS-DMA pieces per wave and tile (slot padded to PPW * WPB KiB)
-    constexpr int TILE_LDS = PPW * WPB * 1024;     // LDS bytes per ring slot
-    constexpr int DIST = BF ? HM_DIST_BF16 : 1;    // tiles in flight ahead of the one being computed
-    constexpr int NBUF = DIST + 1;                 // ring slots
-    constexpr int WAVE_ROWS = 32 * TM;
-    constexpr int BLOCK_ROWS = WPB * WAVE_ROWS;
-    constexpr int NTHREADS = 64 * WPB;
-    static_assert(TILE_BYTES % 1024 == 0, "tiles are moved in 1 KiB pieces");
-    static_assert(DIST * PPW <= 60, "the counted wait must fit vmcnt");
     static_assert(HEAD == 0 || (BF != 0 && SIGN != 0 && MODE == HM_MODE_ARGMIN && PIPE && HEAD == hm_head_steps(NG)),
                   "the head test: bf16 form, lorentz sign, argmin, two accumulator sets, the head set the image's r^ was built for");
-    extern __shared__ __attribute__((aligned(16))) char smem[];   // NBUF * TILE_LDS (+ hist)
+    extern __shared__ __attribute__((aligned(16))) char smem[];   // G::lds_bytes(MODE)
 
     if (p.stop != nullptr && *p.stop != 0u) return;     // a device-resident loop has ended
     if (p.order_seen != nullptr && __hip_atomic_load(p.order_seen, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < p.order_need) {
@@ -145,7 +120,7 @@ __global__ __launch_bounds__(64 * WPB, 2) void hm_scan_kernel(const ScanArgs p)
 
     uint32_t* lhist = nullptr;
     if (MODE == HM_MODE_HIST) {
-        lhist = reinterpret_cast<uint32_t*>(smem + NBUF * TILE_LDS);
+        lhist = reinterpret_cast<uint32_t*>(smem + G::HIST_OFF);
         for (int t = threadIdx.x; t < HM_HIST_BINS; t += NTHREADS) lhist[t] = 0;
     }
 
@@ -336,9 +311,9 @@ __global__ __launch_bounds__(64 * WPB, 2) void hm_scan_kernel(const ScanArgs p)
 
     // The hot form of the bf16 kernel (both groups of a pass run and a finished group is pending): all k-step fragments
     // of the group are in bfr[set] before its MFMAs start -- requested by the previous group (`fresh` = false) -- and
-    // the next group's go out to bfr[set ^ 1] first thing (`prefetch`), so the LDS latency is paid behind fourteen
+    // the next group's go out to bfr[set ^ 1] behind the first k-step, always, so the LDS latency is paid behind fourteen
     // MFMAs instead of in front of every second pair.  The other set's bound-test reduction rides along as in mma_group.
-    auto mma_group_deep = [&](auto set_c, int buf, int sub, bool fresh, bool prefetch, float& ext) __attribute__((always_inline)) {
+    auto mma_group_deep = [&](auto set_c, int buf, int sub, bool fresh, float& ext) __attribute__((always_inline)) {
         constexpr int set = decltype(set_c)::value;
         constexpr int QN = 16 * TM;
         if constexpr (DEEP) {
@@ -373,7 +348,6 @@ __global__ __launch_bounds__(64 * WPB, 2) void hm_scan_kernel(const ScanArgs p)
             // unconditional (behind the last group of a tile the addresses fall into the next slot or the slack behind
             // the ring and the data is never used): a branch here makes hipcc count the waits of the MFMAs below for
             // the path WITHOUT the requests, which in the path with them means waiting for the requests themselves
-            (void)prefetch;
 #pragma unroll
             for (int g = 0; g < NP; ++g) bfr[set ^ 1][g] = frag_at(bt + 32 * RB16, g);
             __builtin_amdgcn_sched_barrier(0);      // the requests stay in front of the remaining MFMAs
@@ -623,10 +597,9 @@ __global__ __launch_bounds__(64 * WPB, 2) void hm_scan_kernel(const ScanArgs p)
         return false;
     };
 
-    // ---- work distribution: block b owns item b of the host's list (hm_prepare_scan); with the item queue (p.dyn) the grid
+    // ---- work distribution: block b owns item b of the host's list (hm_scan_plan.h); with the item queue (p.dyn) the grid
     // is the resident set and every block goes on drawing items of the same list, in order, from the queue word p.q_ctr ----
-    constexpr int QOFF = NBUF * TILE_LDS + 32 * ROW_BYTES + (MODE == HM_MODE_HIST ? (int)sizeof(uint32_t) * HM_HIST_BINS : 0);
-    volatile uint32_t* const qslot = reinterpret_cast<volatile uint32_t*>(smem + QOFF);      // the drawn counter value, for all waves
+    volatile uint32_t* const qslot = reinterpret_cast<volatile uint32_t*>(smem + G::queue_off(MODE));      // the drawn counter value, for all waves
     const bool dyn = (MODE != HM_MODE_HIST) && (p.dyn != 0);
     unsigned long long q_raw = 0ull;     // destination of the asynchronous draw (thread 0)
     if (dyn && threadIdx.x == 0) (void)__hip_atomic_fetch_max(p.q_ctr, p.q_tag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -634,16 +607,7 @@ __global__ __launch_bounds__(64 * WPB, 2) void hm_scan_kernel(const ScanArgs p)
 #pragma unroll 1
     for (;;) {
     bool have = true;                   // the item has tiles right of the diagonal
-    {
-        int it = item, ph = 0;
-        while (ph + 1 < p.n_ph && it >= p.ph_items[ph]) { it -= p.ph_items[ph]; ++ph; }
-        rb = p.ph_rb0[ph] + it / p.ph_chunks[ph];
-        ct0 = p.ph_ctmin[ph] + (it % p.ph_chunks[ph]) * p.ph_ch[ph];
-        ct1 = ct0 + p.ph_ch[ph];
-    }
-    if (ct0 < (rb * BLOCK_ROWS) / COLS) ct0 = (rb * BLOCK_ROWS) / COLS;   // left of the diagonal: no i < j
-    if (ct0 < p.col_begin / COLS) ct0 = p.col_begin / COLS;               // partner rows in front of col_begin are not asked for
-    if (ct1 > p.nct) ct1 = p.nct;
+    HM_SCAN_ITEM_DECODE(p.items, item, BLOCK_ROWS, COLS, p.nct, p.col_begin, rb, ct0, ct1)
     if (ct0 >= ct1) have = false;
 
     // HIST mode visits every sample_stride-th tile only (a cheap estimate of the u' distribution)
@@ -699,9 +663,7 @@ __global__ __launch_bounds__(64 * WPB, 2) void hm_scan_kernel(const ScanArgs p)
             asm volatile("global_atomic_add_x2 %0, %1, %2, off sc0" : "=v"(q_raw) : "v"(p.q_ctr), "v"(1ull) : "memory");
         dma_tile(ct_next, buf_next);
 
-        constexpr bool head_tile = HEAD > 0;     // a head kernel walks every tile this way
-        if constexpr (HEAD > 0) {
-          {
+        if constexpr (HEAD > 0) {           // a head kernel walks every tile this way
             // head walk: the groups of the tile alternate between the accumulator sets; group g's head k-steps carry the
             // reduction of group g - 1's head values, whose test follows.  Nothing is pending across the tile's barrier (the
             // recomputation of a failed group reads its columns from this ring slot): the last group is reduced on its own.
@@ -740,9 +702,6 @@ __global__ __launch_bounds__(64 * WPB, 2) void hm_scan_kernel(const ScanArgs p)
             }
             if (hp) { ++hg; hc += head_finish(std::integral_constant<int, 1>{}, reduce_group(std::integral_constant<int, 1>{}), buf, SUB - 1, j0 + (SUB - 1) * 32) ? 1 : 0; }
             hg_tot += hg; hc_tot += hc;
-          }
-        }
-        if constexpr (head_tile) {
         } else if constexpr (!PIPE) {
             // one accumulator set: MFMAs, then the bound test of the same group (the other resident block of the CU
             // fills the matrix pipe meanwhile); the first fragment of the next group is still requested early
@@ -767,10 +726,10 @@ __global__ __launch_bounds__(64 * WPB, 2) void hm_scan_kernel(const ScanArgs p)
                     const int ja = j0 + 2 * sp * 32, jb = ja + 32;
                     if (wave_active && (ja + 31 > i0w) && pend) {     // both groups of the pass run (jb > ja) and one is pending
                         float ea = 0.0f, eb = 0.0f;
-                        mma_group_deep(std::integral_constant<int, 0>{}, buf, 2 * sp, !deep_valid, true, ea);
+                        mma_group_deep(std::integral_constant<int, 0>{}, buf, 2 * sp, !deep_valid, ea);
                         finish_group(std::integral_constant<int, 1>{}, ea, pend_j0s);
                         const bool more = 2 * sp + 2 < SUB;
-                        mma_group_deep(std::integral_constant<int, 1>{}, buf, 2 * sp + 1, false, more, eb);
+                        mma_group_deep(std::integral_constant<int, 1>{}, buf, 2 * sp + 1, false, eb);
                         finish_group(std::integral_constant<int, 0>{}, eb, ja);
                         pend_j0s = jb;
                         deep_valid = more;                            // bfr[0] holds the fragments of the tile's next group
@@ -876,13 +835,8 @@ __global__ __launch_bounds__(64 * WPB, 2) void hm_scan_kernel(const ScanArgs p)
 template <int NG, int SIGN, int MODE, int BF, int TM, int WPB, int SUB, bool WK = false, int HEAD = 0>
 static hipError_t hm_launch_scan_t(hm_engine* e, const ScanArgs& a, dim3 grid, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1)
 {
-    const size_t row_bytes = BF ? 16 * hm_row16_chunks(NG) : 4 * hm_row_floats(NG);
-    const size_t tile_bytes = (size_t)32 * SUB * row_bytes;
-    const size_t ppw = (tile_bytes / 1024 + WPB - 1) / WPB;
-    size_t lds = ((BF ? HM_DIST_BF16 : 1) + 1) * ppw * WPB * 1024;
-    lds += (size_t)32 * row_bytes;                                          // slack behind the ring: the early request of "the next group's" fragment
-    if (MODE == HM_MODE_HIST) lds += sizeof(uint32_t) * HM_HIST_BINS;      // (HIST mode keeps its bins there; they are only read by that request)
-    lds += 16;                                                              // the item queue's broadcast word
+    using G = ScanGeom<NG, BF, TM, WPB, SUB>;
+    const size_t lds = G::lds_bytes(MODE);
     const void* fn = reinterpret_cast<const void*>(&hm_scan_kernel<NG, SIGN, MODE, BF, TM, WPB, SUB, WK, HEAD>);
     if (lds > 48 * 1024 && e->attr_done.find(fn) == e->attr_done.end()) {     // per engine (= per device), not process-wide
         hipError_t st = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
@@ -900,7 +854,7 @@ static hipError_t hm_launch_scan_t(hm_engine* e, const ScanArgs& a, dim3 grid, h
         auto it = e->scan_slots.find(fn);
         if (it == e->scan_slots.end()) {
             int per_cu = 0;
-            hipError_t st = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, 64 * WPB, lds);
+            hipError_t st = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, G::NTHREADS, lds);
             if (st != hipSuccess) return st;
             it = e->scan_slots.emplace(fn, std::max(1, per_cu) * e->n_cu).first;
         }
@@ -912,8 +866,8 @@ static hipError_t hm_launch_scan_t(hm_engine* e, const ScanArgs& a, dim3 grid, h
             b.q_ctr = e->d_queue + 16 * ((b.ctr64 == e->d_ctr64) ? 0 : 1);      // one word per counter set (the pipelined loop alternates them)
         }
     }
-    if (ev0 != nullptr || ev1 != nullptr) hipExtLaunchKernelGGL((hm_scan_kernel<NG, SIGN, MODE, BF, TM, WPB, SUB, WK, HEAD>), grid, dim3(64 * WPB), lds, s, ev0, ev1, 0, b);
-    else hipLaunchKernelGGL((hm_scan_kernel<NG, SIGN, MODE, BF, TM, WPB, SUB, WK, HEAD>), grid, dim3(64 * WPB), lds, s, b);
+    if (ev0 != nullptr || ev1 != nullptr) hipExtLaunchKernelGGL((hm_scan_kernel<NG, SIGN, MODE, BF, TM, WPB, SUB, WK, HEAD>), grid, dim3(G::NTHREADS), lds, s, ev0, ev1, 0, b);
+    else hipLaunchKernelGGL((hm_scan_kernel<NG, SIGN, MODE, BF, TM, WPB, SUB, WK, HEAD>), grid, dim3(G::NTHREADS), lds, s, b);
     return hipGetLastError();
 }
 
@@ -956,94 +910,65 @@ bool hm_use_bf16(const hm_engine* e)
     return e->d >= 24;
 }
 
-// bf16 block shapes: 0 = 4 waves x 64 rows (256-row blocks, two accumulator sets), 1 = 4 waves x 128 rows (512-row
-// blocks: half the L2 -> LDS fill traffic and half the LDS fragment reads per flop, one accumulator set),
-// 2 = 8 x 64, 3 = 8 x 128 (tuning builds only)
-#ifndef HM_SCAN_ALL_SHAPES
-#define HM_SCAN_ALL_SHAPES 0
-#endif
-#define HM_BF16_CASES(TMv, WPBv)                                                                                           \
-    switch (e->KC) {                                                                                                       \
-        HM_BF16_SMALL(TMv, WPBv)                                                                                           \
-        case 13: return hm_launch_scan_ng<13, 1, TMv, WPBv, HM_SUB_BF16>(e, e->sign_mode, mode, a, grid, s, ev0, ev1);    \
-    }                                                                                                                      \
-    return hipErrorInvalidValue;
-#if HM_SCAN_INSTANTIATE_ALL
-#define HM_BF16_SMALL(TMv, WPBv)                                                                                           \
-        case 2: return hm_launch_scan_ng<2, 1, TMv, WPBv, HM_SUB_BF16>(e, e->sign_mode, mode, a, grid, s, ev0, ev1);      \
-        case 4: return hm_launch_scan_ng<4, 1, TMv, WPBv, HM_SUB_BF16>(e, e->sign_mode, mode, a, grid, s, ev0, ev1);      \
-        case 8: return hm_launch_scan_ng<8, 1, TMv, WPBv, HM_SUB_BF16>(e, e->sign_mode, mode, a, grid, s, ev0, ev1);      \
-        case 14: return hm_launch_scan_ng<14, 1, TMv, WPBv, HM_SUB_BF16>(e, e->sign_mode, mode, a, grid, s, ev0, ev1);
-#else
-#define HM_BF16_SMALL(TMv, WPBv)
-#endif
-
-hipError_t hm_launch_scan(hm_engine* e, int mode, const ScanArgs& a, dim3 grid, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1)
+// bf16 form: the kernels of block shape S (kScanShapes), one per built width.  Shapes other than 0 exist up to
+// HM_SCAN_BIG_MAX_KC chunks only; a width or shape this build has no kernel for is an error, never another kernel.
+template <int S>
+static hipError_t hm_launch_scan_bf16(hm_engine* e, int mode, const ScanArgs& a, dim3 grid, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1)
 {
-    if (a.bf16 && a.shape == 1) { HM_BF16_CASES(4, 4) }
-#if HM_SCAN_ALL_SHAPES
-    if (a.bf16 && a.shape == 2) { HM_BF16_CASES(2, 8) }
-    if (a.bf16 && a.shape == 3) { HM_BF16_CASES(4, 8) }
-    if (a.bf16 && a.shape == 4) { HM_BF16_CASES(3, 4) }
-#endif
-    if (a.bf16) {
-        if (e->KC == 16) {
-#if HM_SCAN_INSTANTIATE_ALL
-            return hm_launch_scan_ng<16, 1, 2, 4, HM_SUB_BF16>(e, e->sign_mode, mode, a, grid, s, ev0, ev1);
-#else
-            return hipErrorInvalidValue;
-#endif
-        }
-        HM_BF16_CASES(2, 4)
-    }
-    switch (e->NG) {
-#if HM_SCAN_INSTANTIATE_ALL
-        case 1: return hm_launch_scan_ng<1, 0, 2, 4, HM_SUB_F32>(e, e->sign_mode, mode, a, grid, s, ev0, ev1);
-        case 2: return hm_launch_scan_ng<2, 0, 2, 4, HM_SUB_F32>(e, e->sign_mode, mode, a, grid, s, ev0, ev1);
-        case 3: return hm_launch_scan_ng<3, 0, 2, 4, HM_SUB_F32>(e, e->sign_mode, mode, a, grid, s, ev0, ev1);
-        case 4: return hm_launch_scan_ng<4, 0, 2, 4, HM_SUB_F32>(e, e->sign_mode, mode, a, grid, s, ev0, ev1);
-        case 6: return hm_launch_scan_ng<6, 0, 2, 4, HM_SUB_F32>(e, e->sign_mode, mode, a, grid, s, ev0, ev1);
-        case 8: return hm_launch_scan_ng<8, 0, 2, 4, HM_SUB_F32>(e, e->sign_mode, mode, a, grid, s, ev0, ev1);
-        case 10: return hm_launch_scan_ng<10, 0, 2, 4, HM_SUB_F32>(e, e->sign_mode, mode, a, grid, s, ev0, ev1);
-        case 13: return hm_launch_scan_ng<13, 0, 2, 4, HM_SUB_F32>(e, e->sign_mode, mode, a, grid, s, ev0, ev1);
-        case 16: return hm_launch_scan_ng<16, 0, 2, 4, HM_SUB_F32>(e, e->sign_mode, mode, a, grid, s, ev0, ev1);
-        case 20: return hm_launch_scan_ng<20, 0, 2, 4, HM_SUB_F32>(e, e->sign_mode, mode, a, grid, s, ev0, ev1);
-        case 28: return hm_launch_scan_ng<28, 0, 2, 4, HM_SUB_F32>(e, e->sign_mode, mode, a, grid, s, ev0, ev1);
-        case 32: return hm_launch_scan_ng<32, 0, 2, 4, HM_SUB_F32>(e, e->sign_mode, mode, a, grid, s, ev0, ev1);
-#endif
-        case 25: return hm_launch_scan_ng<25, 0, 2, 4, HM_SUB_F32>(e, e->sign_mode, mode, a, grid, s, ev0, ev1);
-    }
+    constexpr int TM = kScanShapes[S].tm, WPB = kScanShapes[S].wpb;
+    static_assert(ScanGeom<13, 1, TM, WPB, HM_SUB_BF16>::BLOCK_ROWS == hm_shape_rows(S), "the item plan counts this shape's rows per block");
+#define HM_KC_CASE(KCv)                                                                                                    \
+    case KCv:                                                                                                              \
+        if constexpr (S == 0 || KCv <= HM_SCAN_BIG_MAX_KC)                                                                 \
+            return hm_launch_scan_ng<KCv, 1, TM, WPB, HM_SUB_BF16>(e, e->sign_mode, mode, a, grid, s, ev0, ev1);          \
+        break;
+    switch (e->KC) { HM_SCAN_KC_LIST(HM_KC_CASE, HM_SCAN_WIDTHS_BUILT) }
+#undef HM_KC_CASE
     return hipErrorInvalidValue;
 }
 
-// common argument preparation; returns false when the row range is empty
+hipError_t hm_launch_scan(hm_engine* e, int mode, const ScanArgs& a, dim3 grid, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1)
+{
+    if (a.bf16) {
+        switch (a.shape) {
+            case 0: return hm_launch_scan_bf16<0>(e, mode, a, grid, s, ev0, ev1);
+            case 1: return hm_launch_scan_bf16<1>(e, mode, a, grid, s, ev0, ev1);
+#if HM_SCAN_ALL_SHAPES
+            case 2: return hm_launch_scan_bf16<2>(e, mode, a, grid, s, ev0, ev1);
+            case 3: return hm_launch_scan_bf16<3>(e, mode, a, grid, s, ev0, ev1);
+            case 4: return hm_launch_scan_bf16<4>(e, mode, a, grid, s, ev0, ev1);
+#endif
+        }
+        return hipErrorInvalidValue;
+    }
+    // fp32 form: block shape 0 only
+    constexpr int TM = kScanShapes[0].tm, WPB = kScanShapes[0].wpb;
+#define HM_NG_CASE(NGv) case NGv: return hm_launch_scan_ng<NGv, 0, TM, WPB, HM_SUB_F32>(e, e->sign_mode, mode, a, grid, s, ev0, ev1);
+    switch (e->NG) { HM_SCAN_NG_LIST(HM_NG_CASE, HM_SCAN_WIDTHS_BUILT) }
+#undef HM_NG_CASE
+    return hipErrorInvalidValue;
+}
+
+// common argument preparation; returns false when the row range is empty.  Every decision about the launch's geometry is
+// hm_scan_plan's (hm_scan_plan.h); here the plan is copied into ScanArgs and the engine's pointers and key shifts are filled in
 bool hm_prepare_scan(hm_engine* e, const Bounds& b, int64_t row_begin, int64_t row_end, ScanArgs& a, dim3& grid, int64_t n_limit,
                      int64_t col_begin)
 {
-    // n_limit: search among the first n_limit rows only (rows are only ever appended: the pairs of an earlier table)
-    const int64_t n = (n_limit >= 0 && n_limit < e->n) ? n_limit : e->n;
-    if (row_end < 0 || row_end > n) row_end = n;
-    if (row_begin < 0) row_begin = 0;
-    if (row_end > n - 1) row_end = n - 1;        // the last row has no partner j > i
-    if (row_begin >= row_end) return false;
+    const int bf16 = hm_use_bf16(e) ? 1 : 0;
+    const ScanPlan pl = hm_scan_plan(e->plan, ScanRequest{e->n, row_begin, row_end, n_limit, col_begin, bf16, e->KC});
+    if (!pl.ok) return false;
     memset(&a, 0, sizeof(a));
     a.img = e->img;
     a.img16 = e->img16;
-    a.bf16 = hm_use_bf16(e) ? 1 : 0;
-    // large launches: 512-row blocks halve the L2 -> LDS fill traffic, which is what limits the bf16 form once the
-    // launch tail no longer does (decided by the pairs this launch covers: a row-range search of a sharded run is
-    // a small launch)
-    // (16 chunks would not fit the registers of the 128-row waves)
-    a.shape = (a.bf16 && e->KC <= 14 && hm_pairs_in_range(n, row_begin, row_end) >= e->big_min_rows * (e->big_min_rows - 1) / 2) ? 1 : 0;
-    if (a.bf16 && e->KC <= 14 && e->force_shape >= 0) a.shape = e->force_shape;
-    static const int kShapeRows[5] = {256, 512, 512, 1024, 384};
-    const int block_rows = a.bf16 ? kShapeRows[a.shape] : 256;
-    const int cols = 32 * (a.bf16 ? HM_SUB_BF16 : HM_SUB_F32);     // partner rows per streamed tile
-    a.n = (int)n;
-    a.row_begin = (int)row_begin;
-    a.row_end = (int)row_end;
-    a.rb_first = (int)(row_begin / block_rows);
-    a.nct = (int)((n + cols - 1) / cols);
+    a.bf16 = bf16;
+    a.shape = pl.shape;
+    a.n = pl.n;
+    a.row_begin = pl.row_begin;
+    a.row_end = pl.row_end;
+    a.col_begin = pl.col_begin;
+    a.rb_first = pl.rb_first;
+    a.nct = pl.nct;
+    a.items = pl.items;
     a.u_hi = b.u_hi;
     a.u_lo = b.u_lo;
     a.thr_pos = b.thr_pos;
@@ -1061,55 +986,6 @@ bool hm_prepare_scan(hm_engine* e, const Bounds& b, int64_t row_begin, int64_t r
     a.key_wide = e->key_ib > HM_KEY_IB_NARROW ? 1 : 0;
     a.key_si = 32 - e->key_ib;
     a.key_sj = 2 * e->key_ib - 32;
-    const int rb_last = (int)((row_end - 1) / block_rows);
-    const int nrb = rb_last - a.rb_first + 1;
-    // diagonal advance per row block in tiles (rounded down: the kernel clamps to the exact diagonal)
-    const int tiles_per_rb = std::max(1, block_rows / cols);
-    // column tiles per block: amortise the stationary-row load, but keep enough blocks in flight.
-    // (the knob is in 64-column units)
-    int ch = (a.bf16 ? e->chunk_bf16 : e->chunk_f32) * 64 / cols;
-    if (ch < 1) ch = 1;
-    while (ch > 4 && (int64_t)nrb * ((a.nct + ch - 1) / ch) < 1024) ch >>= 1;
-    // phases: cut the launch's row blocks (top down: longest rows first) at the cumulative work shares; chunk lengths
-    // ch, ch / div[1], ch / div[2], ... (a small launch keeps one phase)
-    a.col_begin = (int)std::max<int64_t>(col_begin, 0);
-    const int ct_lo = a.col_begin / cols;
-    int nph = 1;
-    double share[HM_SCAN_PHASES] = {1.0};
-    int div[HM_SCAN_PHASES];
-    for (int q = 0; q < HM_SCAN_PHASES; ++q) div[q] = 1;
-    if (ch >= 8 && nrb >= 16) {
-        if (e->phases <= 2) {
-            nph = 2;
-            share[0] = 1.0 - e->tail_fraction; share[1] = e->tail_fraction;
-            div[1] = e->tail_div;
-        } else {
-            nph = std::min(e->phases, HM_SCAN_PHASES);
-            double rest = 1.0;
-            for (int q = 0; q < nph - 1; ++q) { share[q] = e->ph_share[q]; rest -= share[q]; }
-            share[nph - 1] = std::max(rest, 0.0);
-            for (int q = 0; q < nph; ++q) div[q] = e->ph_div[q];
-        }
-    }
-    double total = 0.0;
-    for (int rb = a.rb_first; rb <= rb_last; ++rb) total += (double)std::max(0, a.nct - rb * tiles_per_rb);
-    a.n_ph = nph;
-    int rb_at = a.rb_first, n_items = 0;
-    double acc = 0.0, want = 0.0;
-    for (int q = 0; q < nph; ++q) {
-        want += share[q] * total;
-        int rb_end = rb_at;
-        if (q == nph - 1) rb_end = rb_last + 1;
-        else while (rb_end <= rb_last && acc < want) { acc += (double)std::max(0, a.nct - rb_end * tiles_per_rb); ++rb_end; }
-        const int chq = std::max(1, ch / std::max(1, div[q]));
-        a.ph_rb0[q] = rb_at;
-        a.ph_ch[q] = chq;
-        a.ph_ctmin[q] = std::max((int)((int64_t)rb_at * block_rows / cols), ct_lo);
-        a.ph_chunks[q] = std::max(1, (a.nct - a.ph_ctmin[q] + chq - 1) / chq);
-        a.ph_items[q] = (rb_end - rb_at) * a.ph_chunks[q];
-        n_items += a.ph_items[q];
-        rb_at = rb_end;
-    }
-    grid = dim3((unsigned)std::max(1, n_items), 1, 1);
+    grid = dim3((unsigned)pl.n_items, 1, 1);
     return true;
 }
