@@ -32,130 +32,33 @@
 // ranks: rank[i] = #{ j : D[i, j] < D[i, i] } + #{ j < i : D[i, j] == D[i, i] },  D[i, j] = distance(A[i], B[j]), c = 1
 // ------------------------------------------------------------------------------------------------
 // The column direction is the same kernel with A and B exchanged (u is symmetric bit for bit): the owning index is then the
-// column and "j" the row, which is exactly the tie rule of the column ranks.  Two counters per thread, the four waves'
-// partial counts added in a fixed order: no atomics, identical results on every run.
+// column and "j" the row, which is exactly the tie rule of the column ranks.  The walk, its two tile layouts (MAXN = 0: A and
+// B rows in LDS; 32 / 64 / 128: the A row in registers, the step DESIGN.md 5.11 left open) and the fixed-order sum of the four
+// waves' counts live in hm_retrieval_device.h, shared with hm_recon.hip: identical results on every run.
+template <int MAXN>
 __global__ __launch_bounds__(HM_PT_THREADS) void hm_retrieval_rank_kernel(const float* __restrict__ A, const float* __restrict__ B, int64_t n,
                                                                            int64_t lda, int64_t ldb, int d1, int sign_mode,
                                                                            int32_t* __restrict__ rank)
 {
     extern __shared__ float hm_pt_lds[];
-    __shared__ int part_lt[4][HM_PT], part_eq[4][HM_PT];
-    const int SA = hm_pt_stride(d1);
-    float* As = hm_pt_lds;
-    float* Bs = As + HM_PT * SA;
-    const int r = threadIdx.x & 63, q = threadIdx.x >> 6;
+    const int r = threadIdx.x & 63;
     const int64_t i0 = (int64_t)blockIdx.x * HM_PT, i = i0 + r;
-    hm_pt_stage(A, n, lda, d1, i0, As);
+    const auto own = [&](int rr) -> int64_t { return i0 + rr; };
+    hm_rk_layout<MAXN> lay(hm_pt_lds, d1, sign_mode);
+    lay.load_owner(A, n, lda, own);
     // the diagonal D[i, i]: the B rows of the block's own indices, through the same code path as every other pair
-    hm_pt_stage(B, n, ldb, d1, i0, Bs);
+    lay.stage(B, n, ldb, own);
     __syncthreads();
-    const float ucd = hm::clamp_min_one(hm_g_u(As + r * SA, Bs + r * SA, d1, sign_mode));
-    const float dd = hm::dist_from_u(ucd, 1.0f);
-    const bool dnan = ucd != ucd;
-    const float lo = ucd * HM_RT_BAND_LO, hi = ucd * HM_RT_BAND_HI;
+    const hm_rk_pivot_t piv = hm_rk_pivot(hm::clamp_min_one(lay.u(r, r)));
     __syncthreads();
     int lt = 0, eq = 0;
-    for (int64_t j0 = 0; j0 < n; j0 += HM_PT) {
-        hm_pt_stage(B, n, ldb, d1, j0, Bs);
-        __syncthreads();
-        for (int jj = 0; jj < HM_PT_JPT; ++jj) {
-            const int jl = q * HM_PT_JPT + jj;
-            const int64_t j = j0 + jl;
-            if (i >= n || j >= n) continue;
-            const float uc = hm::clamp_min_one(hm_g_u(As + r * SA, Bs + jl * SA, d1, sign_mode));
-            const int first = j < i ? 1 : 0;
-            if (uc != uc) { if (dnan) eq += first; }          // NaN is never less; it equals a NaN diagonal
-            else if (dnan) lt += 1;                            // every number is less than NaN
-            else if (uc == ucd) eq += first;
-            else if (uc < lo) lt += 1;
-            else if (uc > hi) { }
-            else {
-                const float dj = hm::dist_from_u(uc, 1.0f);
-                if (dj < dd) lt += 1;
-                else if (dj == dd) eq += first;
-            }
-        }
-        __syncthreads();
-    }
-    part_lt[q][r] = lt; part_eq[q][r] = eq;
-    __syncthreads();
-    if (q == 0 && i < n) {
-        int s = 0;
-        for (int w = 0; w < 4; ++w) s += part_lt[w][r];
-        for (int w = 0; w < 4; ++w) s += part_eq[w][r];
-        rank[i] = s;
-    }
-}
-
-// ---- the same fold with the A row in registers and B read as 16-byte LDS broadcasts (the step DESIGN.md 5.11 left open) ----
-// The layout itself (hm_rt_u_reg, hm_rt_stage_reg) lives in hm_retrieval_device.h, shared with hm_recon.hip.
-template <int MAXN>
-__global__ __launch_bounds__(HM_PT_THREADS) void hm_retrieval_rank_reg_kernel(const float* __restrict__ A, const float* __restrict__ B,
-                                                                               int64_t n, int64_t lda, int64_t ldb, int d1, int sign_mode,
-                                                                               int32_t* __restrict__ rank)
-{
-    extern __shared__ float hm_pt_lds[];
-    __shared__ int part_lt[4][HM_PT], part_eq[4][HM_PT];
-    constexpr int SB = MAXN + 4;
-    float* Bs = hm_pt_lds;
-    const int r = threadIdx.x & 63, q = threadIdx.x >> 6;
-    const int64_t i0 = (int64_t)blockIdx.x * HM_PT, i = i0 + r;
-    const int ns = d1 - 1;
-    float a[MAXN];
-    const float* arow = A + (i < n ? i : 0) * lda;
-#pragma unroll
-    for (int s = 0; s < MAXN; ++s) a[s] = (s < ns && i < n) ? arow[1 + s] : 0.0f;
-    const float a0 = i < n ? arow[0] : 0.0f;
-    hm_rt_stage_reg<MAXN>(B, n, ldb, d1, i0, Bs);                                  // the diagonal, through the same code path
-    __syncthreads();
-    const float ucd = hm::clamp_min_one(hm_rt_u_reg<MAXN>(a, a0, Bs + r * SB, ns, sign_mode));
-    const float dd = hm::dist_from_u(ucd, 1.0f);
-    const bool dnan = ucd != ucd;
-    const float lo = ucd * HM_RT_BAND_LO, hi = ucd * HM_RT_BAND_HI;
-    __syncthreads();
-    int lt = 0, eq = 0;
-    for (int64_t j0 = 0; j0 < n; j0 += HM_PT) {
-        hm_rt_stage_reg<MAXN>(B, n, ldb, d1, j0, Bs);
-        __syncthreads();
-#pragma unroll 1
-        for (int jj = 0; jj < HM_PT_JPT; ++jj) {
-            const int jl = q * HM_PT_JPT + jj;
-            const int64_t j = j0 + jl;
-            if (j >= n) break;                                                     // wave-uniform
-            const float uc = hm::clamp_min_one(hm_rt_u_reg<MAXN>(a, a0, Bs + jl * SB, ns, sign_mode));
-            if (i >= n) continue;
-            const int first = j < i ? 1 : 0;
-            if (uc != uc) { if (dnan) eq += first; }
-            else if (dnan) lt += 1;
-            else if (uc == ucd) eq += first;
-            else if (uc < lo) lt += 1;
-            else if (uc > hi) { }
-            else {
-                const float dj = hm::dist_from_u(uc, 1.0f);
-                if (dj < dd) lt += 1;
-                else if (dj == dd) eq += first;
-            }
-        }
-        __syncthreads();
-    }
-    part_lt[q][r] = lt; part_eq[q][r] = eq;
-    __syncthreads();
-    if (q == 0 && i < n) {
-        int s = 0;
-        for (int w = 0; w < 4; ++w) s += part_lt[w][r];
-        for (int w = 0; w < 4; ++w) s += part_eq[w][r];
-        rank[i] = s;
-    }
-}
-
-template <int MAXN>
-static int hm_rank_reg_launch(const float* A, const float* B, int64_t n, int64_t lda, int64_t ldb, int d1, int sign_mode, int32_t* rank,
-                              hipStream_t s)
-{
-    const size_t lds = sizeof(float) * HM_PT * (MAXN + 4);
-    hipLaunchKernelGGL(hm_retrieval_rank_reg_kernel<MAXN>, dim3((unsigned)((n + HM_PT - 1) / HM_PT)), dim3(HM_PT_THREADS), lds, s, A, B, n,
-                       lda, ldb, d1, sign_mode, rank);
-    return HM_OK;
+    hm_rk_walk(lay, B, n, ldb, [&](int64_t j, float uc) {
+        const int c = hm_rk_cmp(piv, uc);
+        lt += c & 1;
+        eq += (c >> 1) & (j < i);
+    });
+    hm_rk_reduce(lt, eq);
+    if (threadIdx.x < HM_PT && i < n) rank[i] = lt + eq;
 }
 
 #define HM_RT_LAYOUT_DEFAULT 2                  // faster up to B = 16 384, 8 % slower at 65 536
@@ -164,17 +67,8 @@ static int g_rt_layout = 0;
 static int hm_rank_launch(const float* A, const float* B, int64_t n, int64_t lda, int64_t ldb, int d1, int sign_mode, int32_t* rank,
                           hipStream_t s)
 {
-    const int layout = g_rt_layout ? g_rt_layout : HM_RT_LAYOUT_DEFAULT;
-    if (layout == 2 && d1 >= 9) {
-        if (d1 <= 33) return hm_rank_reg_launch<32>(A, B, n, lda, ldb, d1, sign_mode, rank, s);
-        if (d1 <= 65) return hm_rank_reg_launch<64>(A, B, n, lda, ldb, d1, sign_mode, rank, s);
-        return hm_rank_reg_launch<128>(A, B, n, lda, ldb, d1, sign_mode, rank, s);
-    }
-    const size_t lds = sizeof(float) * hm_pt_lds_floats(d1, false);
-    HM_HIP0(hm_pt_allow_lds(hm_retrieval_rank_kernel, lds));
-    hipLaunchKernelGGL(hm_retrieval_rank_kernel, dim3((unsigned)((n + HM_PT - 1) / HM_PT)), dim3(HM_PT_THREADS), lds, s, A, B, n, lda, ldb, d1,
-                       sign_mode, rank);
-    return HM_OK;
+    return hm_rk_launch([](auto maxn) { return hm_retrieval_rank_kernel<decltype(maxn)::value>; },
+                        g_rt_layout ? g_rt_layout : HM_RT_LAYOUT_DEFAULT, n, d1, s, A, B, n, lda, ldb, d1, sign_mode, rank);
 }
 
 extern "C" int hm_retrieval_ranks(const float* zt_dev, const float* zi_dev, int64_t n, int64_t ld_t, int64_t ld_i, int d1, int sign_mode,

@@ -149,6 +149,26 @@ def test_padded_leading_dimension_unaligned_base_and_node_subsets(oracle, layout
     assert float(flat[0]) == 777.0 and bool((flat[1:].view(v, d1 + pad)[:, d1:] == 777.0).all())
 
 
+@pytest.mark.parametrize("d1", [9, 33, 65, 66])
+def test_both_layouts_in_every_column_class(oracle, layout, d1):
+    """The narrowest rows of the register layout, the MAXN = 32 class at its upper end and both sides of the 64 / 128 boundary,
+    every graph kind, and a node subset whose slots end inside a block."""
+    v = 130
+    x = RC.table(v, d1, seed=5)
+    dist = RC.distances(oracle, x)
+    xd = torch.from_numpy(x).to(DEV)
+    nodes = np.random.RandomState(d1).permutation(v)[:37]
+    for kind in RC.KINDS:
+        row_ptr, col = RC.csr(kind, v)
+        got, c = gpu_counts(xd, row_ptr, col)
+        want = RC.truth_counts(dist, row_ptr, col)
+        check_counts(f"{kind} d1={d1}", got, want)
+        check_metrics(f"{kind} d1={d1}", GM().metrics_from_counts(c), RC.metrics(want))
+        want = RC.truth_counts(dist, row_ptr, col, nodes)
+        assert want["anchors"].size % 64 != 0
+        check_counts(f"subset {kind} d1={d1}", gpu_counts(xd, row_ptr, col, nodes)[0], want)
+
+
 def test_node_mapping_places_the_graph_in_a_larger_table(oracle):
     """The 63-node tree on rows 3 k + 1 of a 200-row table: the other rows are candidates in every ranking, never anchors."""
     n, edges = GC.tree_graph()
@@ -207,6 +227,43 @@ def test_every_output_element_is_written_and_nothing_else(oracle, layout, d1):
     _lib.check(L.hm_recon_counts(_ptr(xd), d1, v, d1, _ptr(ints[0]), _ptr(ints[1]), _ptr(ints[2]), _ptr(rp), s, v, _ptr(ints[3]),
                                  _ptr(ints[4]), _ptr(ints[5]), _ptr(ints[6]), _ptr(u), _stream_of(xd)))
     assert ints[3:, 1].cpu().tolist() == [-1, -1, -1, -1] and ints[3:, 0].cpu().tolist()[0] == int(want["less_all"][0])
+
+
+@pytest.mark.parametrize("d1", [33, 129])
+def test_slots_outside_the_table_are_dead_and_their_neighbours_are_not(oracle, layout, d1):
+    """The C ABI with anchors and pivots below 0 and at or past V, in the first and in the last (partial) block: those slots
+    get -1, -1 and a NaN u and are never dereferenced; every other slot keeps its all-keys counts and the bits of its u."""
+    from hyptokenizer_amd import _lib
+    from hyptokenizer_amd.engine import _ptr, _stream_of
+    L = _lib.load()
+    v = 130
+    x = RC.table(v, d1, seed=6)
+    row_ptr, col = RC.csr("sparse", v)
+    want = RC.truth_counts(RC.distances(oracle, x), row_ptr, col)
+    s = col.size
+    assert s > 128 and s % 64 != 0
+    xd = torch.from_numpy(x).to(DEV)
+    rp = torch.from_numpy(row_ptr).to(DEV)
+    anchors, pivots = torch.from_numpy(want["anchors"]).to(DEV), torch.from_numpy(want["pivots"]).to(DEV)
+    seg = torch.from_numpy(np.repeat(np.arange(v), np.diff(row_ptr)).astype(np.int32)).to(DEV)
+
+    def run():
+        ints = torch.full((4, s), 0x7B7B7B7B, dtype=torch.int32, device=DEV)
+        u = torch.full((s,), 777.0, device=DEV)
+        _lib.check(L.hm_recon_counts(_ptr(xd), d1, v, d1, _ptr(anchors), _ptr(pivots), _ptr(seg), _ptr(rp), s, v, _ptr(ints[0]),
+                                     _ptr(ints[1]), _ptr(ints[2]), _ptr(ints[3]), _ptr(u), _stream_of(xd)))
+        return ints.cpu().numpy(), u.cpu().numpy()
+
+    clean, clean_u = run()
+    assert np.array_equal(clean[0], want["less_all"]) and np.array_equal(clean[1], want["equal_all"])
+    dead = {1: ("a", v), 5: ("p", -1), 63: ("a", -7), 64: ("p", v), 70: ("p", 2 ** 31 - 1), s - 1: ("a", v + 64)}
+    for e, (which, value) in dead.items():
+        (anchors if which == "a" else pivots)[e] = value
+    out, u = run()
+    at = np.array(sorted(dead))
+    alive = np.setdiff1d(np.arange(s), at)
+    assert (out[:, at] == -1).all() and np.isnan(u[at]).all()
+    assert np.array_equal(out[:2, alive], clean[:2, alive]) and np.array_equal(u[alive].view(np.uint32), clean_u[alive].view(np.uint32))
 
 
 def test_a_graph_without_edges_returns_nan():

@@ -114,6 +114,22 @@ def test_both_rank_layouts_equal_the_truth(oracle, mode):
         R().set_rank_layout(3)
 
 
+@pytest.mark.parametrize("mode", MODES)
+def test_both_rank_layouts_on_one_partial_block_and_on_strided_inputs(oracle, mode):
+    """A single block with dead owner rows (n = 1, 63) in every column class of the register layout; layout 2 asked of rows
+    narrower than 9 columns (they take the LDS layout); the strided and column-major inputs under both layouts."""
+    try:
+        for layout in (1, 2):
+            R().set_rank_layout(layout)
+            for n, d1 in ((1, 9), (63, 9), (1, 33), (63, 33), (1, 129), (63, 129), (64, 8)):
+                rs = np.random.RandomState(91 * n + d1)
+                a, b = RC.special_pairs(rs, n, d1 - 1, scale=0.5 if d1 > 9 else 1.0, noise=0.7)
+                check_ranks(oracle, a, b, mode)
+            test_ranks_of_non_contiguous_inputs(oracle, mode)
+    finally:
+        R().set_rank_layout(0)
+
+
 # ---- 3. k-NN -------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("mode", MODES)
 def test_knn_equals_the_truth(oracle, mode):

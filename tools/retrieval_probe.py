@@ -40,14 +40,14 @@ SIGN = "lorentz"
 #: what hipcc -Rpass-analysis=kernel-resource-usage reports for gfx950 (recorded next to the timings; not measured here).
 #: blocks_per_cu: by LDS (160 KiB per CU) and registers (256 threads = one wave per SIMD and block), at the d1 / k named
 KERNEL_RESOURCES = {
-    "hm_retrieval_rank_kernel (layout 1)": {"vgprs": 68, "scratch_bytes": 0, "waves_per_simd_by_registers": 7, "static_lds_bytes": 2048,
-                                            "dynamic_lds_bytes": "4 * (2 * 64 * (d1 | 1) + 136)", "blocks_per_cu": {"d1=65": 4, "d1=129": 2}},
-    "hm_retrieval_rank_reg_kernel<32> (layout 2, d1 <= 33)": {"vgprs": 104, "scratch_bytes": 0, "waves_per_simd_by_registers": 4,
-                                                              "static_lds_bytes": 2048, "dynamic_lds_bytes": 4 * 64 * 36, "blocks_per_cu": 4},
-    "hm_retrieval_rank_reg_kernel<64> (layout 2, d1 <= 65)": {"vgprs": 146, "scratch_bytes": 0, "waves_per_simd_by_registers": 3,
-                                                              "static_lds_bytes": 2048, "dynamic_lds_bytes": 4 * 64 * 68, "blocks_per_cu": 3},
-    "hm_retrieval_rank_reg_kernel<128> (layout 2, d1 <= 129)": {"vgprs": 213, "scratch_bytes": 0, "waves_per_simd_by_registers": 2,
-                                                                "static_lds_bytes": 2048, "dynamic_lds_bytes": 4 * 64 * 132, "blocks_per_cu": 2},
+    "hm_retrieval_rank_kernel<0> (layout 1)": {"vgprs": 68, "scratch_bytes": 0, "waves_per_simd_by_registers": 7, "static_lds_bytes": 2048,
+                                               "dynamic_lds_bytes": "4 * (2 * 64 * (d1 | 1) + 136)", "blocks_per_cu": {"d1=65": 4, "d1=129": 2}},
+    "hm_retrieval_rank_kernel<32> (layout 2, d1 <= 33)": {"vgprs": 104, "scratch_bytes": 0, "waves_per_simd_by_registers": 4,
+                                                          "static_lds_bytes": 2048, "dynamic_lds_bytes": 4 * 64 * 36, "blocks_per_cu": 4},
+    "hm_retrieval_rank_kernel<64> (layout 2, d1 <= 65)": {"vgprs": 145, "scratch_bytes": 0, "waves_per_simd_by_registers": 3,
+                                                          "static_lds_bytes": 2048, "dynamic_lds_bytes": 4 * 64 * 68, "blocks_per_cu": 3},
+    "hm_retrieval_rank_kernel<128> (layout 2, d1 <= 129)": {"vgprs": 213, "scratch_bytes": 0, "waves_per_simd_by_registers": 2,
+                                                            "static_lds_bytes": 2048, "dynamic_lds_bytes": 4 * 64 * 132, "blocks_per_cu": 2},
     "hm_knn_kernel": {"vgprs": 79, "scratch_bytes": 0, "waves_per_simd_by_registers": 6, "static_lds_bytes": 1536,
                       "dynamic_lds_bytes": "4 * (2 * 64 * (d1 | 1) + 64 * 65 + 2 * 64 * (k | 1))",
                       "blocks_per_cu": {"d1=65,k=10": 2, "d1=129,k=128": 1}},
