@@ -59,6 +59,7 @@ EXPORTED_SYMBOLS = (
     "hm_negsample_set_csr", "hm_negsample_sample",
     "hm_centroid_fwd", "hm_centroid_bwd", "hm_debug_centroid_form",
     "hm_recon_slots", "hm_recon_counts", "hm_debug_recon_layout",
+    "hm_gromov_delta_i16", "hm_gromov_delta_f32", "hm_gromov_workspace_bytes", "hm_debug_gromov_form",
 )
 
 
@@ -208,6 +209,11 @@ def load() -> C.CDLL:
     L.hm_recon_slots.argtypes = [vp, vp, i64, i64, vp, i64, vp, i64, vp, vp, vp, vp]
     L.hm_recon_counts.argtypes = [vp, i64, i64, C.c_int, vp, vp, vp, vp, i64, i64, vp, vp, vp, vp, vp, vp]
     L.hm_debug_recon_layout.argtypes = [C.c_int]
+    L.hm_gromov_delta_i16.argtypes = [vp, i64, i64, vp, i64, vp, vp, vp, vp]
+    L.hm_gromov_delta_f32.argtypes = [vp, i64, i64, vp, i64, vp, vp, vp, vp]
+    L.hm_gromov_workspace_bytes.restype = i64
+    L.hm_gromov_workspace_bytes.argtypes = [i64, i64]
+    L.hm_debug_gromov_form.argtypes = [C.c_int]
     L.hm_negsample_create.argtypes = [C.POINTER(vp), C.c_int]
     L.hm_negsample_destroy.argtypes = [vp]
     L.hm_negsample_check_csr.argtypes = [vp, vp, i64]
@@ -224,7 +230,7 @@ def load() -> C.CDLL:
     L.hm_scan_totals.argtypes = [vp, C.POINTER(C.c_double), pi64, pi64, C.c_int]
     for name in EXPORTED_SYMBOLS:
         fn = getattr(L, name)
-        if name not in ("hm_last_error", "hm_rows", "hm_tokenize_table_capacity"):
+        if name not in ("hm_last_error", "hm_rows", "hm_tokenize_table_capacity", "hm_gromov_workspace_bytes"):
             fn.restype = C.c_int
     _lib = L
     return L

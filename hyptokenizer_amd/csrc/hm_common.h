@@ -18,6 +18,7 @@
 //   hm_poincare.hip, hm_riemann.hip   Poincare-ball primitives; fused Riemannian optimiser steps (lane groups of hm_rowgroup.h)
 //   hm_contrastive.hip   fused InfoNCE / triplet loss
 //   hm_retrieval.hip   recall@K ranks and exact k nearest keys
+//   hm_gromov.hip      Gromov delta-hyperbolicity of a distance matrix (engine-free); hm_gromov_plan.h: its host-side plan (no HIP)
 //   hm_tokenize.hip    batch form of HyperbolicTokenizer.tokenize (engine-free, like the four below)
 //   hm_greedy.hip, hm_pairfreq.hip, hm_ngram.hip   the text side: greedy longest-match counts, adjacent-pair and n-gram
 //                   histograms of a corpus; hm_classmin.hip: per-class minima of the pair distance.  These four share

@@ -7,7 +7,9 @@ line, two node names separated by a tab; node indices are then the order of firs
 ``[V, dim + 1]``), ``nodes.json`` (node names in row order) and ``train_log.json`` (hyper-parameters and the mean loss of every
 epoch) to ``--output-dir``; with ``--eval-pairs N > 0`` also ``distortion_stats.json`` from ``compute_distortion`` over N
 sampled pairs; with ``--eval-reconstruction`` also ``reconstruction_stats.json``: ``reconstruction_metrics`` (mean rank and mAP
-of the graph's edges) of the trained table and, under ``"initial"``, of the table training started from.  The reference has no counterpart: it never trains its embeddings.
+of the graph's edges) of the trained table and, under ``"initial"``, of the table training started from; with
+``--eval-hyperbolicity N > 0`` also ``hyperbolicity_stats.json``: Gromov's delta, its relative form and the curvature estimate
+ of the graph metric and of the trained table's distances on the same sample of N nodes.  The reference has no counterpart: it never trains its embeddings.
 """
 from __future__ import annotations
 
@@ -21,6 +23,8 @@ import typer
 
 from hyptokenizer_amd.embedding.graph_embedding import GraphEmbeddingResult, fit_graph_embedding, init_table
 from hyptokenizer_amd.embedding.graph_metrics import reconstruction_metrics
+from hyptokenizer_amd.embedding.hyperbolicity import curvature_estimate, embedding_hyperbolicity, graph_hyperbolicity
+from hyptokenizer_amd.graph_paths import GraphPaths
 from hyptokenizer_amd.scripts.eval_hierarchy import compute_distortion, load_wordnet_graph, set_seeds
 
 logging.basicConfig(level=logging.INFO, format="%(asctime)s - %(name)s - %(levelname)s - %(message)s")
@@ -68,7 +72,8 @@ def load_graph(graph_path: str):
 def train_graph_embeddings(graph_path: str, output_dir: str, dim: int = 10, epochs: int = 50, batch_size: int = 1024,
                            num_negatives: int = 50, lr: float = 0.3, burn_in_epochs: int = 10, burn_in_factor: float = 0.1,
                            optimizer: str = "rsgd", init_scale: float = 1e-3, seed: int = 0, curvature: float = 1.0,
-                           eval_pairs: int = 0, log_every: int = 1, eval_reconstruction: bool = False) -> GraphEmbeddingResult:
+                           eval_pairs: int = 0, log_every: int = 1, eval_reconstruction: bool = False,
+                           eval_hyperbolicity: int = 0) -> GraphEmbeddingResult:
     graph = load_graph(graph_path)
     params = dict(dim=dim, epochs=epochs, batch_size=batch_size, num_negatives=num_negatives, lr=lr, burn_in_epochs=burn_in_epochs,
                   burn_in_factor=burn_in_factor, optimizer=optimizer, init_scale=init_scale, seed=seed, c=curvature)
@@ -93,7 +98,31 @@ def train_graph_embeddings(graph_path: str, output_dir: str, dim: int = 10, epoc
         with open(os.path.join(output_dir, "reconstruction_stats.json"), "w") as f:
             json.dump(stats, f, indent=4)
         logger.info(f"Reconstruction: mean rank {stats['mean_rank']:.3f}, mAP {stats['map']:.4f} over {stats['num_pairs']} pairs")
+    if eval_hyperbolicity > 0:
+        with open(os.path.join(output_dir, "hyperbolicity_stats.json"), "w") as f:
+            json.dump(hyperbolicity_stats(graph, result, eval_hyperbolicity, seed, curvature), f, indent=4)
     return result
+
+
+def hyperbolicity_stats(graph, result: GraphEmbeddingResult, num_samples: int, seed: int, curvature: float) -> Dict[str, object]:
+    """Gromov's delta of the graph metric and of the trained table's distances on one node sample: the sample the graph side
+    keeps (its largest component among the drawn nodes), mapped to table rows."""
+    paths = GraphPaths(graph, device=result.table.device)
+    g = graph_hyperbolicity(paths, num_samples=num_samples, seed=seed)
+    rows = [result.node_mapping[paths.node_names[int(k)]] for k in g.nodes_used]
+    t = embedding_hyperbolicity(result.table, nodes=rows, num_samples=len(rows), base_points=g.base_positions.tolist(), seed=seed,
+                                c=curvature)
+
+    def side(h):
+        return {"delta": h.delta, "delta_rel": h.delta_rel, "diameter": h.diameter, "n_used": h.n_used,
+                # null: no diameter; "inf": delta 0, a tree fits every curvature (strict JSON has no infinity)
+                "curvature_estimate": None if h.delta_rel != h.delta_rel else
+                ("inf" if h.delta_rel == 0.0 else curvature_estimate(h.delta_rel)),
+                "witness": list(h.witness)}
+    stats = {"num_samples": int(num_samples), "seed": int(seed), "graph": side(g), "embedding": side(t)}
+    logger.info(f"Hyperbolicity: graph delta {g.delta} (relative {g.delta_rel:.4f}), embedding delta {t.delta:.4f} "
+                f"(relative {t.delta_rel:.4f}) on {g.n_used} nodes")
+    return stats
 
 
 def main(
@@ -112,12 +141,13 @@ def main(
     curvature: float = 1.0,
     eval_pairs: int = 0,
     eval_reconstruction: bool = False,
+    eval_hyperbolicity: int = 0,
 ) -> None:
     """Train hyperbolic embeddings of a graph."""
     train_graph_embeddings(graph_path=graph_path, output_dir=output_dir, dim=dim, epochs=epochs, batch_size=batch_size,
                            num_negatives=num_negatives, lr=lr, burn_in_epochs=burn_in_epochs, burn_in_factor=burn_in_factor,
                            optimizer=optimizer, init_scale=init_scale, seed=seed, curvature=curvature, eval_pairs=eval_pairs,
-                           eval_reconstruction=eval_reconstruction)
+                           eval_reconstruction=eval_reconstruction, eval_hyperbolicity=eval_hyperbolicity)
 
 
 if __name__ == "__main__":

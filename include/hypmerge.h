@@ -750,6 +750,40 @@ int hm_recon_counts(const float* x_dev, int64_t ld, int64_t V, int d1, const int
  * rows always take layout 1). */
 int hm_debug_recon_layout(int layout);
 
+/* Gromov delta-hyperbolicity: how far a metric is from a tree's, per base point, as one fused walk over the
+ * (max, min) semiring without a Gromov-product matrix.  d_dev is a row-major [n, n] distance matrix with leading dimension ld,
+ * of which only the upper triangle is read: D(i, j) := d[min(i, j), max(i, j)]; the diagonal is read as it is given.
+ * base_dev int32 [n_base] holds positions w in 0..n-1; per base the call writes one value and one witness (i, j, k), int32
+ * [n_base, 3].
+ *   hm_gromov_delta_i16 (int16 distances):  B_w(i, j) = D(i, w) + D(j, w) - D(i, j), twice the Gromov product, an integer.
+ *     Precondition: 0 <= d <= 32767 and the triangle inequality holds, so 0 <= B <= 65534 fits 16 unsigned bits.
+ *     value (int32) = 2 delta_w = max_{i <= j} [ max_k min(B(i, k), B(k, j)) - B(i, j) ].
+ *   hm_gromov_delta_f32 (float distances):  A_w(i, j) = 0.5f * ((D(i, w) + D(j, w)) - D(i, j)) + 0.0f, evaluated in exactly
+ *     this order without contraction (the + 0.0f stores -0 as +0).  Precondition: every entry is finite.
+ *     value (float) = delta_w = max_{i <= j} fl( max_k min(A(i, k), A(k, j)) - A(i, j) ); max and min are exact, so the value
+ *     has the bits of a float32 restatement in numpy.
+ * Witness: among the maximising pairs the smallest i, then the smallest j >= i, then the smallest k that attains the inner
+ * maximum of that pair.  The maximum of delta_w over all w is the four-point delta; a tree metric gives 0.
+ * A base outside [0, n) is never dereferenced: value -1, witness (-1, -1, -1).  With a precondition violated the values are
+ * unspecified, but no index is ever derived from matrix data, so such a call cannot read out of bounds.
+ * workspace: hm_gromov_workspace_bytes(n, n_base) bytes of device memory = 16 bytes per base and 128 x 128 tile of the upper
+ * triangle (one record per block; -1 for sizes the calls refuse), not initialised by the caller, free for reuse once the call
+ * has run.  Every output is written once by one thread, no atomics: two calls give the same bytes.
+ * Engine-independent; errors through hm_last_error(NULL); asynchronous on `stream`.  HM_E_ARG before the device is touched for
+ * a NULL pointer, n outside 1..32768, ld < n, n_base < 0 or n_base > n.  n_base == 0 launches nothing and returns HM_OK.
+ * Replaces: nothing the reference runs (its AdaptiveCurvatureTokenizer, the one place that would choose a curvature, cannot
+ * be run: SURVEY F8). */
+int hm_gromov_delta_i16(const int16_t* d_dev, int64_t n, int64_t ld, const int32_t* base_dev, int64_t n_base, int32_t* value_out_dev,
+                        int32_t* witness_out_dev, void* workspace, void* stream);
+int hm_gromov_delta_f32(const float* d_dev, int64_t n, int64_t ld, const int32_t* base_dev, int64_t n_base, float* value_out_dev,
+                        int32_t* witness_out_dev, void* workspace, void* stream);
+int64_t hm_gromov_workspace_bytes(int64_t n, int64_t n_base);
+/* Test / tuning hook (results never depend on it while the preconditions hold): the path of hm_gromov_delta_i16 from now on,
+ * process-wide.  0 = the default (the packed path, chosen by measurement: DESIGN.md 5.20), 1 = 32-bit integer min / max, one
+ * output per lane (the path hm_gromov_delta_f32 always takes, on order-preserving keys), 2 = packed 16-bit min / max, two
+ * outputs per lane. */
+int hm_debug_gromov_form(int form);
+
 /* Test hook: pretend the previous refresh ended on this emission cut (bits of u'); the next whole-table top-k
  * search starts from it as given and has to notice by itself when it is too tight. */
 int hm_debug_force_cut(hm_engine* e, uint32_t cut_bits, int64_t k, float c);
