@@ -228,6 +228,8 @@ struct hm_engine {
     unsigned long long scan_tag = 0;      // launch tags of the item queue (monotonic per engine)
     std::map<const void*, int> scan_slots; // resident blocks per scan kernel instantiation on this engine's device
     int head = HM_SCAN_HEAD;              // knob `head`: k-steps of the argmin scan's head test (hm_head_steps); 0 = the kernels without it
+    int head_ring = HM_SCAN_HEAD_RING_DEFAULT;   // knob `head_ring`: the head kernels' partner-tile ring (kScanRings, hm_scan_geom.h; 0 = the ring of every other kernel)
+    int64_t argmin_col_begin = 0;         // knob `argmin_col_begin` (tests): hm_pairwise_argmin only looks at partners j >= this (a fresh engine: the seed knows nothing of it)
     bool head_force = false;              // knob `head_force` (tests): every eligible argmin launch takes the head kernel, whatever hm_head_live expects
     int64_t head_merges = 0;              // merged rows appended since the table was set or an existing row changed (hm_head_live)
     int64_t max_rows = 0, rows_alloc = 0, n = 0;
@@ -366,8 +368,10 @@ Bounds hm_bounds(float thr, float c);
 
 // ---- hm_scan.hip ----
 bool hm_use_bf16(const hm_engine* e);
+// mode: the search the launch is for (HM_MODE_*): the plan keeps the block shape a head kernel exists for where an argmin
+// launch will take one
 bool hm_prepare_scan(hm_engine* e, const Bounds& b, int64_t row_begin, int64_t row_end, ScanArgs& a, dim3& grid, int64_t n_limit = -1,
-                     int64_t col_begin = 0);
+                     int64_t col_begin = 0, int mode = HM_MODE_TOPK);
 hipError_t hm_launch_scan(hm_engine* e, int mode, const ScanArgs& a, dim3 grid, hipStream_t s, hipEvent_t ev0 = nullptr,
                           hipEvent_t ev1 = nullptr);
 // (hm_pairs_in_range: hm_scan_plan.h)

@@ -162,7 +162,7 @@ static int hm_issue_step(hm_engine* e, const StdLoop& L, int64_t k, int64_t coun
     const int set = piped ? (int)(k & 1) : 0;
     ScanArgs a; dim3 grid;
     // (pipelined) scan_old(k): all rows but the newest (step 0: the whole table)
-    if (!hm_prepare_scan(e, L.b, 0, -1, a, grid, piped && k > 0 ? e->n - 1 : -1)) return hm_fail(e, HM_E_STATE, "hm_std_merge_steps: empty scan");
+    if (!hm_prepare_scan(e, L.b, 0, -1, a, grid, piped && k > 0 ? e->n - 1 : -1, 0, HM_MODE_ARGMIN)) return hm_fail(e, HM_E_STATE, "hm_std_merge_steps: empty scan");
     a.stop = &e->d_loop->stop;
     if (piped) {
         a.ent = set ? e->ent2 : e->ent;

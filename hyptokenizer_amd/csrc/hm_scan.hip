@@ -86,15 +86,27 @@ __device__ __forceinline__ void hm_dma_run(const char* src, uint32_t dst)
 // <= (1 + 2^-6) rmax2 (r^ exceeds ||x_R|| by at most two bf16 roundings): (kterms - 7) * 1.016 <= kterms for kterms <= 437.
 // So head_f <= H_b + (that part) <= u_c + delta: a group whose lanes all have head_f >= bound holds no pair that the
 // complete chain could have reported.  tests/test_scan_head_bound.py checks the inequality in numpy.
-template <int NG, int SIGN, int MODE, int BF, int TM, int WPB, int SUB, bool WK = false, int HEAD = 0>
+//
+// RING > 0 (head kernels only; kScanRings of hm_scan_geom.h): a head kernel's wave is done with a 128-column tile in a
+// fraction of the time the tile takes to land, so its ring keeps 64-column slots (RSUB = 2 groups: one pass of the head
+// walk) and DIST = 3 or 4 of them in flight.  What changes with the depth: the item's run is counted in ring tiles; the
+// counted waits leave (DIST - 1) tiles' pieces outstanding -- a wave's own number of pieces, which with exact shares
+// depends on the (wave-uniform) wave index, so the waits branch on it and every immediate stays a constant; the
+// asynchronous key load is picked up DIST - 1 tiles after it went out (vector-memory loads return in order: by then the
+// wait of that tile has passed the tile requested right behind it); and the queue draw is picked up behind the run's
+// closing vmcnt(0).
+template <int NG, int SIGN, int MODE, int BF, int TM, int WPB, int SUB, bool WK = false, int HEAD = 0, int RING = 0>
 __global__ __launch_bounds__(64 * WPB, 2) void hm_scan_kernel(const ScanArgs p)
 {
     static_assert(SUB % 2 == 0, "the two accumulator sets alternate between column groups: an even number per tile");
+    static_assert(RING == 0 || HEAD > 0, "rings other than 0 belong to the head kernels");
     constexpr bool PIPE = (TM <= HM_SCAN_PIPE_MAX_TM);   // two accumulator sets fit the registers (128 stationary rows per wave: one set)
     // the geometry of this instantiation (hm_scan_geom.h: sizes, ring, LDS map)
-    using G = ScanGeom<NG, BF, TM, WPB, SUB>;
+    using G = ScanGeom<NG, BF, TM, WPB, SUB, RING>;
     constexpr int COLS = G::COLS, RS = G::RS, RB16 = G::RB16, TILE_BYTES = G::TILE_BYTES, NP = G::NP;
     constexpr int PPW = G::PPW, TILE_LDS = G::TILE_LDS, DIST = G::DIST, NBUF = G::NBUF;
+    constexpr int RSUB = G::RSUB;                  // 32-column groups per ring slot (SUB: per tile of the item plan)
+    static_assert(RSUB % 2 == 0, "the head walk takes the groups of a slot in pairs");
     constexpr int WAVE_ROWS = G::WAVE_ROWS, BLOCK_ROWS = G::BLOCK_ROWS, NTHREADS = G::NTHREADS;
     constexpr bool HALF_LAST = (BF != 0) && (NG & 1);   // the last k-step covers one chunk only (8 K-slots)
     constexpr int TCH = RS / 4 - 1;                // fp32 image: chunk index of the time group
@@ -212,11 +224,22 @@ __global__ __launch_bounds__(64 * WPB, 2) void hm_scan_kernel(const ScanArgs p)
     // ---- LDS-DMA of one tile: wave w moves the PPW consecutive pieces [w * PPW, (w + 1) * PPW), four per
     // statement, through inline asm so that hipcc neither sees nor drains them; pieces past NPIECE (slot padding)
     // read the first KiB of the next tile: in bounds (the image is allocated with slack rows), unused.
+    // Exact shares (G::EXACT): the slot is the tile, the first PREM waves move PQ + 1 pieces and the others PQ -- two code
+    // sites chosen by the wave-uniform `wave`, so that each wave's piece count is a constant its counted waits can name.
+    constexpr int PQ = G::NPIECE / WPB, PREM = G::EXACT ? G::NPIECE % WPB : 0;
     auto dma_tile = [&](int ct, int buf) __attribute__((always_inline)) {
+        if constexpr (G::EXACT) {
+            const int first = wave * PQ + (wave < PREM ? wave : PREM);
+            const char* src = reinterpret_cast<const char*>(p.img16) + (int64_t)ct * TILE_BYTES + lane * 16 + first * 1024;
+            const uint32_t dst = __builtin_amdgcn_readfirstlane(lds_base + (uint32_t)buf * (uint32_t)TILE_LDS + (uint32_t)first * 1024u);
+            if (PREM != 0 && wave < PREM) hm_dma_run<PQ + 1>(src, dst);
+            else hm_dma_run<PQ>(src, dst);
+        } else {
         const char* src = (BF ? reinterpret_cast<const char*>(p.img16) : reinterpret_cast<const char*>(p.img)) +
                           (int64_t)ct * TILE_BYTES + lane * 16 + wave * (PPW * 1024);
         const uint32_t dst = __builtin_amdgcn_readfirstlane(lds_base + (uint32_t)buf * (uint32_t)TILE_LDS + (uint32_t)wave * (PPW * 1024u));
         hm_dma_run<PPW>(src, dst);
+        }
     };
 
     // ---- per-group pieces ----
@@ -607,7 +630,14 @@ __global__ __launch_bounds__(64 * WPB, 2) void hm_scan_kernel(const ScanArgs p)
 #pragma unroll 1
     for (;;) {
     bool have = true;                   // the item has tiles right of the diagonal
-    HM_SCAN_ITEM_DECODE(p.items, item, BLOCK_ROWS, COLS, p.nct, p.col_begin, rb, ct0, ct1)
+    HM_SCAN_ITEM_DECODE(p.items, item, BLOCK_ROWS, G::PLAN_COLS, p.nct, p.col_begin, rb, ct0, ct1)
+    if constexpr (COLS != G::PLAN_COLS) {
+        // the run in ring tiles: the plan's tiles are whole numbers of them; the clamps again at the finer grain
+        ct0 *= G::PLAN_COLS / COLS;
+        ct1 *= G::PLAN_COLS / COLS;
+        if (ct0 < p.col_begin / COLS) ct0 = p.col_begin / COLS;
+        if (ct1 > (p.n + COLS - 1) / COLS) ct1 = (p.n + COLS - 1) / COLS;
+    }
     if (ct0 >= ct1) have = false;
 
     // HIST mode visits every sample_stride-th tile only (a cheap estimate of the u' distribution)
@@ -629,6 +659,14 @@ __global__ __launch_bounds__(64 * WPB, 2) void hm_scan_kernel(const ScanArgs p)
     auto tile_at = [&](int t) { return ct0 + t * ct_step; };
 
     // ring prologue: tiles 0 .. DIST-1 in flight (a repeat of the last tile when the run is shorter), tile 0 landed
+    if constexpr (RING > 0) {
+        // the tiles the run has, no repeats (the loop below requests none either); everything lands before the loop is
+        // entered -- the wait hipcc can see (below) would drain the prologue's tiles anyway, once per item
+#pragma unroll
+        for (int q = 0; q < DIST; ++q)
+            if (q < ntile) dma_tile(tile_at(q), q);
+        __builtin_amdgcn_s_waitcnt(0x0F70);
+    } else {
 #pragma unroll
     for (int q = 0; q < DIST; ++q) dma_tile(tile_at(q < ntile ? q : ntile - 1), q);
     if (DIST - 1 <= 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -637,12 +675,14 @@ __global__ __launch_bounds__(64 * WPB, 2) void hm_scan_kernel(const ScanArgs p)
     // vmcnt(N) instructions that also wait for the ring's LDS-DMA (which it cannot see) on every iteration.
     // A wait it can see, here, settles them before the loop is entered.
     if (DIST == 1) __builtin_amdgcn_s_waitcnt(0x0F70);      // vmcnt(0), expcnt / lgkmcnt untouched (gfx9 encoding)
+    }
     __syncthreads();
 
     bool pend = false;               // a finished group waits in the other accumulator set for its bound test
     bool deep_valid = false;         // bfr[0] holds the fragments of the group about to run (requested by its predecessor)
     int pend_j0s = 0;
     int buf = 0;                     // ring slot of tile t
+    int gk_due = 0;                  // RING > 0: the tile behind whose wait the key load in flight is complete
 
     for (int t = 0; t < ntile; ++t) {
         const int ct = tile_at(t);
@@ -654,14 +694,34 @@ __global__ __launch_bounds__(64 * WPB, 2) void hm_scan_kernel(const ScanArgs p)
         // running best key, re-read every 8th tile by a load the compiler does not see (it would wait for it with
         // vmcnt(0) inside the MFMA loop and so drain the ring): the value is picked up behind this iteration's own
         // counted wait.  Issued ahead of the tile's DMA, so that wait covers it.
-        if (MODE == HM_MODE_ARGMIN && (t & 7) == 0) {
+        // (RING > 0: every 8th plan tile, as ever; picked up DIST - 1 tiles later, or behind the run's last wait)
+        // RING > 0: the key load stays in flight for DIST - 1 tiles and the waits in between are several statements, so its
+        // destination cannot be a variable: hipcc is free to copy a variable between two statements, and a copy made
+        // before the data is there carries the register's old content (seen: the queue draw's copy in front of the wait).
+        // Both results land in fixed registers the compiler never allocates in these kernels -- v[252:255], named as clobbers
+        // here and where they are read, above the 187 VGPRs the head kernels use (reported with the kernels' resources:
+        // a build whose own allocation reached v252 must not ship) -- and are moved out behind the wait that covers them.
+        if (MODE == HM_MODE_ARGMIN && (t & (8 * (G::PLAN_COLS / COLS) - 1)) == 0) {
+            if constexpr (RING > 0) {
+                asm volatile("global_load_dwordx2 v[252:253], %0, off sc1" : : "v"(&p.ctr64[1]) : "memory", "v252", "v253");
+                gk_due = t + DIST - 1;
+            } else {
             asm volatile("global_load_dwordx2 %0, %1, off sc1" : "=v"(gk_raw) : "v"(&p.ctr64[1]) : "memory");
+            }
             gk_pending = true;
         }
         // item queue: the next item is drawn during this item's last tile (picked up behind the same counted wait)
-        if (dyn && t == ntile - 1 && threadIdx.x == 0)
+        if (dyn && t == ntile - 1 && threadIdx.x == 0) {
+            if constexpr (RING > 0)
+                asm volatile("global_atomic_add_x2 v[254:255], %0, %1, off sc0" : : "v"(p.q_ctr), "v"(1ull) : "memory", "v254", "v255");
+            else
             asm volatile("global_atomic_add_x2 %0, %1, %2, off sc0" : "=v"(q_raw) : "v"(p.q_ctr), "v"(1ull) : "memory");
+        }
+        if constexpr (RING > 0) {
+            if (t + DIST < ntile) dma_tile(ct_next, buf_next);      // (no repeats: the waits below count what is left of the run)
+        } else {
         dma_tile(ct_next, buf_next);
+        }
 
         if constexpr (HEAD > 0) {           // a head kernel walks every tile this way
             // head walk: the groups of the tile alternate between the accumulator sets; group g's head k-steps carry the
@@ -670,7 +730,7 @@ __global__ __launch_bounds__(64 * WPB, 2) void hm_scan_kernel(const ScanArgs p)
             bool hp = false;
             int hg = 0, hc = 0;          // groups of this tile that ran / that had to be recomputed
 #pragma unroll 1
-            for (int sp = 0; sp < SUB / 2; ++sp) {
+            for (int sp = 0; sp < RSUB / 2; ++sp) {
                 {
                     const int sub = 2 * sp;
                     const int j0s = j0 + sub * 32;
@@ -700,7 +760,7 @@ __global__ __launch_bounds__(64 * WPB, 2) void hm_scan_kernel(const ScanArgs p)
                     hp = do_c;
                 }
             }
-            if (hp) { ++hg; hc += head_finish(std::integral_constant<int, 1>{}, reduce_group(std::integral_constant<int, 1>{}), buf, SUB - 1, j0 + (SUB - 1) * 32) ? 1 : 0; }
+            if (hp) { ++hg; hc += head_finish(std::integral_constant<int, 1>{}, reduce_group(std::integral_constant<int, 1>{}), buf, RSUB - 1, j0 + (RSUB - 1) * 32) ? 1 : 0; }
             hg_tot += hg; hc_tot += hc;
         } else if constexpr (!PIPE) {
             // one accumulator set: MFMAs, then the bound test of the same group (the other resident block of the CU
@@ -771,11 +831,49 @@ __global__ __launch_bounds__(64 * WPB, 2) void hm_scan_kernel(const ScanArgs p)
         }
 
         // tile t+1 has landed (this wave's pieces) -- and so has the key load, if one was issued
+        if constexpr (RING > 0) {
+            // the counted wait that leaves the pieces of at most `tiles` (wave-uniform; DIST - 1 at most count) of this wave's
+            // tiles outstanding; a key load or a queue draw among the outstanding only makes the count stricter
+            auto ring_wait = [&](int tiles) __attribute__((always_inline)) {
+                auto wait_p = [&](auto p_c) __attribute__((always_inline)) {
+                    constexpr int P = decltype(p_c)::value;
+                    static_assert((DIST - 1) * P <= 60, "the counted wait must fit vmcnt");
+                    if (tiles >= 3 && DIST > 3) asm volatile("s_waitcnt vmcnt(%0)" : : "n"(3 * P) : "memory");
+                    else if (tiles >= 2 && DIST > 2) asm volatile("s_waitcnt vmcnt(%0)" : : "n"(2 * P) : "memory");
+                    else if (tiles >= 1 && DIST > 1) asm volatile("s_waitcnt vmcnt(%0)" : : "n"(P) : "memory");
+                    else asm volatile("s_waitcnt vmcnt(0)" : : : "memory");
+                };
+                static_assert(DIST <= 4, "ring_wait writes out the depths");
+                if constexpr (PREM != 0) {
+                    if (wave < PREM) wait_p(std::integral_constant<int, PQ + 1>{});
+                    else wait_p(std::integral_constant<int, PQ>{});
+                } else {
+                    wait_p(std::integral_constant<int, G::EXACT ? PQ : PPW>{});
+                }
+            };
+            // tiles t + 2 .. of the run may stay in flight, DIST - 1 of them at most; behind the last tile nothing does
+            ring_wait(ntile - 2 - t);
+            // the key load is complete once the wait has passed the tile requested right behind it (tile t_issue + DIST: loads
+            // return in order), or behind the run's last wait, a vmcnt(0); the draw goes out during the last tile only
+            if (gk_pending && (t >= gk_due || t == ntile - 1)) {
+                uint32_t klo, khi;
+                asm volatile("v_mov_b32 %0, v252\n\tv_mov_b32 %1, v253" : "=v"(klo), "=v"(khi) : : "memory", "v252", "v253");
+                gk_raw = ((unsigned long long)khi << 32) | klo;
+                if (gk_raw < gk) gk = gk_raw;
+                gk_pending = false;
+            }
+            if (dyn && t == ntile - 1 && threadIdx.x == 0) {
+                uint32_t qlo, qhi;
+                asm volatile("v_mov_b32 %0, v254\n\tv_mov_b32 %1, v255" : "=v"(qlo), "=v"(qhi) : : "memory", "v254", "v255");
+                q_raw = ((unsigned long long)qhi << 32) | qlo;
+            }
+        } else {
         if (DIST - 1 <= 0) asm volatile("s_waitcnt vmcnt(0)" : "+v"(gk_raw), "+v"(q_raw) : : "memory");
         else asm volatile("s_waitcnt vmcnt(%2)" : "+v"(gk_raw), "+v"(q_raw) : "n"((DIST - 1) * PPW) : "memory");
         if (MODE == HM_MODE_ARGMIN && gk_pending) {
             if (gk_raw < gk) gk = gk_raw;                   // the key only ever decreases
             gk_pending = false;
+        }
         }
         if (dyn && t == ntile - 1 && threadIdx.x == 0) { qslot[0] = (uint32_t)q_raw; qslot[1] = (uint32_t)(q_raw >> 32); }
         __syncthreads();                                     // ... and every wave's; all reads of slot `buf` done
@@ -788,7 +886,8 @@ __global__ __launch_bounds__(64 * WPB, 2) void hm_scan_kernel(const ScanArgs p)
         }
     }
 
-    if (DIST > 1) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); __syncthreads(); }   // nothing of this run may land later
+    // nothing of this run may land later (RING > 0: its last wait was a vmcnt(0) already)
+    if (DIST > 1 && RING == 0) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); __syncthreads(); }
     }   // have
 
     if (!dyn) break;
@@ -832,12 +931,13 @@ __global__ __launch_bounds__(64 * WPB, 2) void hm_scan_kernel(const ScanArgs p)
 // ------------------------------------------------------------------------------------------------
 // launch
 // ------------------------------------------------------------------------------------------------
-template <int NG, int SIGN, int MODE, int BF, int TM, int WPB, int SUB, bool WK = false, int HEAD = 0>
+template <int NG, int SIGN, int MODE, int BF, int TM, int WPB, int SUB, bool WK = false, int HEAD = 0, int RING = 0>
 static hipError_t hm_launch_scan_t(hm_engine* e, const ScanArgs& a, dim3 grid, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1)
 {
-    using G = ScanGeom<NG, BF, TM, WPB, SUB>;
+    using G = ScanGeom<NG, BF, TM, WPB, SUB, RING>;
     const size_t lds = G::lds_bytes(MODE);
-    const void* fn = reinterpret_cast<const void*>(&hm_scan_kernel<NG, SIGN, MODE, BF, TM, WPB, SUB, WK, HEAD>);
+    static_assert(RING == 0 || G::lds_bytes(MODE) <= HM_LDS_PER_BLOCK, "a deeper ring keeps two blocks per CU");
+    const void* fn = reinterpret_cast<const void*>(&hm_scan_kernel<NG, SIGN, MODE, BF, TM, WPB, SUB, WK, HEAD, RING>);
     if (lds > 48 * 1024 && e->attr_done.find(fn) == e->attr_done.end()) {     // per engine (= per device), not process-wide
         hipError_t st = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (st != hipSuccess) return st;
@@ -866,8 +966,8 @@ static hipError_t hm_launch_scan_t(hm_engine* e, const ScanArgs& a, dim3 grid, h
             b.q_ctr = e->d_queue + 16 * ((b.ctr64 == e->d_ctr64) ? 0 : 1);      // one word per counter set (the pipelined loop alternates them)
         }
     }
-    if (ev0 != nullptr || ev1 != nullptr) hipExtLaunchKernelGGL((hm_scan_kernel<NG, SIGN, MODE, BF, TM, WPB, SUB, WK, HEAD>), grid, dim3(G::NTHREADS), lds, s, ev0, ev1, 0, b);
-    else hipLaunchKernelGGL((hm_scan_kernel<NG, SIGN, MODE, BF, TM, WPB, SUB, WK, HEAD>), grid, dim3(G::NTHREADS), lds, s, b);
+    if (ev0 != nullptr || ev1 != nullptr) hipExtLaunchKernelGGL((hm_scan_kernel<NG, SIGN, MODE, BF, TM, WPB, SUB, WK, HEAD, RING>), grid, dim3(G::NTHREADS), lds, s, ev0, ev1, 0, b);
+    else hipLaunchKernelGGL((hm_scan_kernel<NG, SIGN, MODE, BF, TM, WPB, SUB, WK, HEAD, RING>), grid, dim3(G::NTHREADS), lds, s, b);
     return hipGetLastError();
 }
 
@@ -883,8 +983,15 @@ static hipError_t hm_launch_scan_ng(hm_engine* e, int sign, int mode, const Scan
             constexpr int HD = (BF != 0 && TM <= HM_SCAN_PIPE_MAX_TM) ? hm_head_steps(NG) : 0;
             if constexpr (HD > 0) {
                 if (hm_head_live(e)) {
-                    if (a.key_wide) return hm_launch_scan_t<NG, 1, HM_MODE_ARGMIN, BF, TM, WPB, SUB, true, HD>(e, a, grid, s, ev0, ev1);
-                    return hm_launch_scan_t<NG, 1, HM_MODE_ARGMIN, BF, TM, WPB, SUB, false, HD>(e, a, grid, s, ev0, ev1);
+                    // the head kernels' ring (kScanRings; knob `head_ring`): the one place that gives a kernel another ring than 0
+#define HM_HEAD_RING_CASE(R)                                                                                               \
+    case R:                                                                                                                \
+        if (a.key_wide) return hm_launch_scan_t<NG, 1, HM_MODE_ARGMIN, BF, TM, WPB, SUB, true, HD, R>(e, a, grid, s, ev0, ev1); \
+        return hm_launch_scan_t<NG, 1, HM_MODE_ARGMIN, BF, TM, WPB, SUB, false, HD, R>(e, a, grid, s, ev0, ev1);
+                    static_assert(HM_SCAN_RINGS == 3, "one case per ring");
+                    switch (e->head_ring) { HM_HEAD_RING_CASE(0) HM_HEAD_RING_CASE(1) HM_HEAD_RING_CASE(2) }
+#undef HM_HEAD_RING_CASE
+                    return hipErrorInvalidValue;
                 }
             }
             if (a.key_wide) return hm_launch_scan_t<NG, 1, HM_MODE_ARGMIN, BF, TM, WPB, SUB, true>(e, a, grid, s, ev0, ev1);
@@ -952,10 +1059,12 @@ hipError_t hm_launch_scan(hm_engine* e, int mode, const ScanArgs& a, dim3 grid, 
 // common argument preparation; returns false when the row range is empty.  Every decision about the launch's geometry is
 // hm_scan_plan's (hm_scan_plan.h); here the plan is copied into ScanArgs and the engine's pointers and key shifts are filled in
 bool hm_prepare_scan(hm_engine* e, const Bounds& b, int64_t row_begin, int64_t row_end, ScanArgs& a, dim3& grid, int64_t n_limit,
-                     int64_t col_begin)
+                     int64_t col_begin, int mode)
 {
     const int bf16 = hm_use_bf16(e) ? 1 : 0;
-    const ScanPlan pl = hm_scan_plan(e->plan, ScanRequest{e->n, row_begin, row_end, n_limit, col_begin, bf16, e->KC});
+    // (the condition under which hm_launch_scan_ng picks a head kernel for a 64-row-wave launch)
+    const int head = (mode == HM_MODE_ARGMIN && bf16 && e->sign_mode && hm_head_steps(e->KC) > 0 && hm_head_live(e)) ? 1 : 0;
+    const ScanPlan pl = hm_scan_plan(e->plan, ScanRequest{e->n, row_begin, row_end, n_limit, col_begin, bf16, e->KC, head});
     if (!pl.ok) return false;
     memset(&a, 0, sizeof(a));
     a.img = e->img;

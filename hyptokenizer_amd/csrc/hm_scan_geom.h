@@ -64,24 +64,56 @@ HM_HOST_DEVICE_INLINE constexpr int hm_shape_rows_max(int shape = 0)
 }
 static_assert(hm_shape_rows_max() == HM_MAX_BLOCK_ROWS, "the images are allocated with one largest block of slack rows");
 
+// ---- partner-tile rings: index = the kernels' RING argument, entry = {sub, dist, exact}.  A ring slot holds `sub`
+// 32-column groups (0: the kernel's SUB), `dist` tiles are in flight ahead of the computed one (0: HM_DIST_BF16 / 1), and
+// with `exact` every wave moves its exact share of the tile's pieces and a slot is as large as the tile (otherwise every
+// wave moves PPW pieces and the slot is padded to PPW * WPB KiB).  Ring 0 is every kernel's but the head kernels' of the
+// argmin scan, which compute a 64-column tile in a third of the time its landing takes: they keep narrower slots and
+// more of them in flight in the same LDS (two blocks per CU: at most 80 KiB per block).  The item plan's tile
+// (hm_scan_plan.h) stays 32 * SUB columns for every ring; a kernel with narrower slots walks an item's run in its own tiles.
+//   1  64-column slots padded to 16 KiB: 4 slots, 3 tiles (40 KB at 13 chunks) in flight
+//   2  64-column slots of the tile's own 13 KiB: 5 slots, 4 tiles (53 KB) in flight
+struct ScanRing { int sub, dist, exact; };
+#define HM_SCAN_RINGS 3
+constexpr ScanRing kScanRings[HM_SCAN_RINGS] = {{0, 0, 0}, {2, 3, 0}, {2, 4, 1}};
+// the head kernels' ring (knob `head_ring`).  Measured at 50 000 rows, interleaved in one process (profiles/scan_head_ring_ab.json):
+// ring 1 takes 2.5 - 4 % off the scan launch of ring 0; ring 2 -- a third more in flight and no padding traffic -- none
+#define HM_SCAN_HEAD_RING_DEFAULT 1
+#define HM_LDS_PER_BLOCK (80 * 1024)  // half of a CU's 160 KiB: what a block may use with two blocks resident
+
 // ---- what follows from a kernel's template arguments.  LDS map of a block (dynamic shared memory, from offset 0):
 //   ring    NBUF slots of TILE_LDS bytes: the streamed partner tiles
 //   slack   32 rows: the early request of "the next group's" first fragments behind the last group of the last slot lands
 //           here and is never used.  HIST mode keeps its HM_HIST_BINS bins at the same offset (they are only read by that
 //           request) and the slack's bytes behind them
 //   queue   16 bytes: the item queue's broadcast word
-template <int NG, int BF, int TM, int WPB, int SUB>
+template <int NG, int BF, int TM, int WPB, int SUB, int RING = 0>
 struct ScanGeom {
-    static constexpr int COLS = 32 * SUB;                   // partner rows per streamed tile
+    static_assert(RING >= 0 && RING < HM_SCAN_RINGS && (RING == 0 || BF != 0), "rings other than 0: bf16 form");
+    static constexpr int RSUB = kScanRings[RING].sub ? kScanRings[RING].sub : SUB;   // 32-column groups per ring slot
+    static constexpr bool EXACT = kScanRings[RING].exact != 0;
+    static constexpr int PLAN_COLS = 32 * SUB;              // partner rows per tile of the item plan
+    static constexpr int COLS = 32 * RSUB;                  // partner rows per streamed tile
+    static_assert(SUB % RSUB == 0, "an item's run of plan tiles is a whole number of ring tiles");
     static constexpr int RS = hm_row_floats(NG);            // fp32 image: floats per row
     static constexpr int RB16 = 16 * hm_row16_chunks(NG);   // bf16 image: bytes per row (NG chunks of 8 bf16 [+ the [x0 fp32] chunk])
     static constexpr int ROW_BYTES = BF ? RB16 : RS * 4;
     static constexpr int TILE_BYTES = COLS * ROW_BYTES;
     static constexpr int NP = BF ? (NG + 1) / 2 : NG + 1;   // k-steps: fp32: NG spatial groups + time; bf16: two chunks per step
     static constexpr int NPIECE = TILE_BYTES / 1024;        // 1 KiB pieces per tile
-    static constexpr int PPW = (NPIECE + WPB - 1) / WPB;    // LDS-DMA pieces per wave and tile (slot padded to PPW * WPB KiB)
-    static constexpr int TILE_LDS = PPW * WPB * 1024;       // LDS bytes per ring slot
-    static constexpr int DIST = BF ? HM_DIST_BF16 : 1;      // tiles in flight ahead of the one being computed
+    static constexpr int PPW = (NPIECE + WPB - 1) / WPB;    // LDS-DMA pieces per wave and tile (slot padded to PPW * WPB KiB), at most
+    // exact shares: wave w moves wave_pieces(w) pieces from piece wave_first(w) on (the first NPIECE % WPB waves one more)
+    HM_HOST_DEVICE_INLINE static constexpr int wave_pieces(int w) { return EXACT ? NPIECE / WPB + (w < NPIECE % WPB ? 1 : 0) : PPW; }
+    HM_HOST_DEVICE_INLINE static constexpr int wave_first(int w)
+    {
+        return EXACT ? w * (NPIECE / WPB) + (w < NPIECE % WPB ? w : NPIECE % WPB) : w * PPW;
+    }
+    static constexpr int TILE_LDS = EXACT ? TILE_BYTES : PPW * WPB * 1024;       // LDS bytes per ring slot
+    // tiles in flight ahead of the one being computed.  A ring other than 0 asks for its depth and gets what fits the
+    // block's half of a CU's LDS beside the slack and the queue word (wide rows: 17 chunks keep 3 in flight where 13 keep 4)
+    static constexpr int SLOTS_MAX = (HM_LDS_PER_BLOCK - 32 * ROW_BYTES - 16) / TILE_LDS;
+    static constexpr int DIST = RING == 0 ? (BF ? HM_DIST_BF16 : 1)
+                                          : (kScanRings[RING].dist + 1 <= SLOTS_MAX ? kScanRings[RING].dist : (SLOTS_MAX > 2 ? SLOTS_MAX - 1 : 1));
     static constexpr int NBUF = DIST + 1;                   // ring slots
     static constexpr int WAVE_ROWS = 32 * TM;
     static constexpr int BLOCK_ROWS = WPB * WAVE_ROWS;

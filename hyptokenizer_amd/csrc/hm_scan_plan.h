@@ -39,7 +39,8 @@ struct ScanPlanKnobs {
 
 // what a search asks for: a table of n rows, rows [row_begin, row_end) against partners j >= col_begin among the first
 // n_limit rows (n_limit < 0: all; rows are only ever appended: the pairs of an earlier table), in which prefilter form
-struct ScanRequest { int64_t n, row_begin, row_end, n_limit, col_begin; int bf16, KC; };
+// head: 1 = an argmin search whose launch takes a head kernel (hm_scan.hip, HEAD > 0: 64-row waves only)
+struct ScanRequest { int64_t n, row_begin, row_end, n_limit, col_begin; int bf16, KC; int head = 0; };
 // ok = false: the row range is empty (nothing else is set)
 struct ScanPlan {
     bool ok;
@@ -72,6 +73,9 @@ inline ScanPlan hm_scan_plan(const ScanPlanKnobs& k, const ScanRequest& rq)
     // a small launch)
     const bool shaped = rq.bf16 && rq.KC <= HM_SCAN_BIG_MAX_KC;
     pl.shape = (shaped && hm_pairs_in_range(n, row_begin, row_end) >= k.big_min_rows * (k.big_min_rows - 1) / 2) ? 1 : 0;
+    // ... but not where the launch takes a head kernel: that one exists for 256-row blocks only and beats the 512-row
+    // kernel without the test at every size (100 000 rows: 0.569 against 0.773 ms per scan, profiles/scan_head_ring_ab.json)
+    if (rq.head) pl.shape = 0;
     if (shaped && k.force_shape >= 0) pl.shape = k.force_shape;
     const int block_rows = hm_shape_rows(pl.shape);
     const int cols = 32 * (rq.bf16 ? HM_SUB_BF16 : HM_SUB_F32);     // partner rows per streamed tile

@@ -614,7 +614,7 @@ extern "C" int hm_pairwise_argmin_dev(hm_engine* e, float c, float thr, int64_t 
     ScanArgs a; dim3 grid;
     const int64_t req_rb = std::max<int64_t>(row_begin, 0), req_re = (row_end < 0 || row_end >= e->n) ? -1 : row_end;
     const bool skip_init = e->st.take_arm(req_rb, req_re);
-    if (b.none || e->n < 2 || !hm_prepare_scan(e, b, row_begin, row_end, a, grid)) {
+    if (b.none || e->n < 2 || !hm_prepare_scan(e, b, row_begin, row_end, a, grid, -1, 0, HM_MODE_ARGMIN)) {
         HM_HIP(hipMemsetAsync(rec_dev, 0, sizeof(ArgminRec), s));        // found = 0
         return HM_OK;
     }
@@ -660,7 +660,7 @@ extern "C" int hm_pairwise_argmin(hm_engine* e, float c, float thr, int64_t row_
     // the range as asked, "to the end" normalised (the table grows between searches): what "same range" means
     const int64_t req_rb = std::max<int64_t>(row_begin, 0), req_re = (row_end < 0 || row_end >= e->n) ? -1 : row_end;
     const bool skip_init = e->st.take_arm(req_rb, req_re);
-    if (b.none || e->n < 2 || !hm_prepare_scan(e, b, row_begin, row_end, a, grid)) return HM_OK;
+    if (b.none || e->n < 2 || !hm_prepare_scan(e, b, row_begin, row_end, a, grid, -1, e->argmin_col_begin, HM_MODE_ARGMIN)) return HM_OK;
     if (e->force_exact || e->st.straight_to_exact(thr)) {
         // this table's searches are known to end in the prefilter-free path (hm_exact.hip): no scan attempts first
         float d1 = 0.f; int32_t i1 = -1, j1 = -1; int64_t n1 = 0, cnt1 = 0;

@@ -792,7 +792,9 @@ int hm_debug_force_cut(hm_engine* e, uint32_t cut_bits, int64_t k, float c);
  * launches covering at least the pairs of this many rows), "chunk", "tail", "tail_div", "shape", "incr_topk", "phases" / "ph_share0..4" / "ph_div1..5" (item list of the scan), "dyn" (0: one block per item instead of the resident grid
  * that draws its items from a device counter) and "dyn_slots" (size of that resident grid; 0 = what the device holds), "head" (k-steps of the argmin scan's
  * head test: the value the library was built with, 3, or 0 for the kernels without the test; the library launches the head kernels
- * only where it expects a tight bound -- from the third merge into a table on), "head_force" (1: on every eligible launch), "pipeline" (0: the standard loop
+ * only where it expects a tight bound -- from the third merge into a table on), "head_force" (1: on every eligible launch), "head_ring" (the head kernels' partner-tile
+ * ring: 1 (default) = 64-column padded slots, three in flight; 2 = 64-column slots of the tile's own size, four in flight; 0 = the 128-column
+ * ring of every other kernel), "pipeline" (0: the standard loop
  * strictly sequential), "pipeline_pairs", "pipe_fault_at", "exact_search" (1: every top-k / count through the prefilter-free
  * exact path that is otherwise the last resort of a search whose survivors fit no emission cut), "kc_even" (default knob only:
  * bf16 image rows padded to whole 16-slot k-steps), and the two default knobs of the graph component above.  hm_debug_set_default_knob applies to every
