@@ -11,12 +11,11 @@
 //   a_k    = ([k = 0] - p_k) / (sqrt(c) sqrt(u_k^2 - 1)), p = softmax(-d) over the live slots; a_k = 0 where u_k <= 1
 //   grad   anchor: sum_k a_k (x_k0, -x_ks);  partner k: a_k (x_u0, -x_us)            (Euclidean, -J x = (x0, -xs))
 //
-// Layout: the lane groups of hm_rowgroup.h, 16 (d <= 64) or 32 lanes per row, scalar form (the spatial part starts one column
-// into the row), the time column a per-row scalar beside the slots as in hm_riemann.hip.  A group keeps the anchor row in
-// registers and walks partners with EL_FLIGHT partner rows loaded before the first is used.  Two forms (hm_debug_edge_loss_form):
-//   form 0  one GROUP per sample: the group walks all P partners (4 or 2 samples per wave);
-//   form 1  one WAVE per sample: its S = 4 or 2 groups take the partners k = g, g + S, g + 2 S, ... and combine d_min, the sum
-//           of exponentials and the anchor's gradient by butterflies across the wave -- S times the waves, P / S the walk.
+// Layout: Lorentz rows gathered on the lane groups of hm_rowgroup.h.  A group keeps the anchor row in
+// registers and walks partners in flights of EL_FLIGHT rows (rg_gather's).  Two forms (hm_debug_edge_loss_form, rg_split_map):
+//   form 0  one GROUP per sample: the group walks all P partners;
+//   form 1  one WAVE per sample: its S groups take the partners k = g, g + S, g + 2 S, ... and combine d_min, the sum of
+//           exponentials and the anchor's gradient by butterflies across the wave -- S times the waves, P / S the walk.
 // Below, "position" i of group g is partner k = g + S i (form 0: S = 1, g = 0).
 //   forward   pass 1: u_k by the whole group (el_canon_sum: hm_halfwave_sum's chains laid over the group's slots), parked in
 //             lane k % G, which evaluates d_k once and stores u_k to the weights w [B, P];
@@ -29,7 +28,7 @@
 
 #pragma clang fp contract(off)
 
-#define EL_THREADS 64                                         // one wave per block: 4 or 2 samples, so that small batches spread
+#define EL_THREADS HM_RG_WAVE                                 // one wave per block: 4 or 2 samples, so that small batches spread
 #define EL_FLIGHT 4                                           // partner rows in flight per group
 
 struct ElArgs {
@@ -45,7 +44,6 @@ struct ElArgs {
     float sqrt_c;
 };
 
-__device__ __forceinline__ bool el_in(int64_t i, int64_t V) { return i >= 0 && i < V; }
 __device__ __forceinline__ float el_pick(const float (&p)[4], int j) { return j == 0 ? p[0] : j == 1 ? p[1] : j == 2 ? p[2] : p[3]; }
 
 // Sum of the row's d products pr (element e in slot e >> lsh of lane e & (G - 1); slots past d hold 0) in the order of
@@ -125,25 +123,6 @@ __device__ __forceinline__ float el_sum(int width, float a)
     return a;
 }
 
-// lane -> (sample, group of the sample, lane of the group); a block is one wave
-__device__ __forceinline__ RgMap el_map(const ElArgs& a, int& gid, int& S)
-{
-    if (!a.split) {
-        gid = 0;
-        S = 1;
-        return rg_map(a.lsh, 0, a.B);
-    }
-    RgMap m;
-    m.lsh = a.lsh;
-    m.vec = 0;
-    m.sub = (int)(threadIdx.x & ((1u << a.lsh) - 1u));
-    m.row = (int64_t)blockIdx.x;
-    m.live = m.row < a.B;
-    gid = (int)(threadIdx.x >> a.lsh);
-    S = EL_THREADS >> a.lsh;
-    return m;
-}
-
 // the sample of this group: its anchor and whether it is served
 struct ElSample {
     const int64_t* ix;
@@ -157,19 +136,21 @@ __device__ __forceinline__ ElSample el_sample(const ElArgs& a, const RgMap& q)
     s.ix = a.index + q.row * (int64_t)(2 + a.K);
     s.iu = q.live ? s.ix[0] : -1;
     const int64_t iv = q.live ? s.ix[1] : -1;
-    s.ok = q.live && el_in(s.iu, a.V) && el_in(iv, a.V);
+    s.ok = q.live && rg_in(s.iu, a.V) && rg_in(iv, a.V);
     return s;
 }
 
 __global__ __launch_bounds__(EL_THREADS) void hm_el_fwd_kernel(const ElArgs a)
 {
     int gid, S;
-    const RgMap q = el_map(a, gid, S);
+    const RgMap q = rg_split_map(a.lsh, a.split, a.B, gid, S);
     const ElSample s = el_sample(a, q);
     const int G = 1 << a.lsh, d = a.d, P = 1 + a.K;
     const int Pp = (P + S - 1) / S, width = G * S;               // positions per group; lanes that share the sample
     RgMap qa = q;
     qa.live = s.ok;
+    // The rows of this kernel are written out, not RgRow / rg_gather: with the rows in structs the compiler emits the same
+    // 4508 instructions in a schedule that measures 0.6 - 0.9 % slower.
     const float* xr = a.x + (s.ok ? s.iu : 0) * a.ld;
     float xs[4];
     const float x0 = s.ok ? xr[0] : 1.0f;
@@ -189,7 +170,7 @@ __global__ __launch_bounds__(EL_THREADS) void hm_el_fwd_kernel(const ElArgs a)
             for (int r = 0; r < EL_FLIGHT; ++r) {
                 const int k = gid + S * (c0 + kk + r);
                 idx[r] = (s.ok && k < P) ? s.ix[1 + k] : -1;
-                lv[r] = el_in(idx[r], a.V);
+                lv[r] = rg_in(idx[r], a.V);
             }
 #pragma unroll
             for (int r = 0; r < EL_FLIGHT; ++r) {
@@ -221,7 +202,7 @@ __global__ __launch_bounds__(EL_THREADS) void hm_el_fwd_kernel(const ElArgs a)
     float sum = 0.0f;
     for (int c0 = 0; c0 < Pp; c0 += G) {
         const int k = gid + S * (c0 + q.sub);
-        if (s.ok && k < P && el_in(s.ix[1 + k], a.V)) sum = sum + expf(dmin - hm::dist_from_u(wr[k], a.sqrt_c));
+        if (s.ok && k < P && rg_in(s.ix[1 + k], a.V)) sum = sum + expf(dmin - hm::dist_from_u(wr[k], a.sqrt_c));
     }
     sum = el_sum(width, sum);
     const float lse = logf(sum) - dmin;
@@ -232,7 +213,7 @@ __global__ __launch_bounds__(EL_THREADS) void hm_el_fwd_kernel(const ElArgs a)
         const int k = gid + S * (c0 + q.sub);
         if (!q.live || k >= P) continue;
         float ak = 0.0f;
-        if (s.ok && el_in(s.ix[1 + k], a.V)) {
+        if (s.ok && rg_in(s.ix[1 + k], a.V)) {
             const float u = wr[k];
             if (u > 1.0f) {
                 const float p = expf(dmin - hm::dist_from_u(u, a.sqrt_c)) / sum;
@@ -243,78 +224,58 @@ __global__ __launch_bounds__(EL_THREADS) void hm_el_fwd_kernel(const ElArgs a)
     }
 }
 
-// one value row: time by the group's first lane, the spatial part by rg_store
-__device__ __forceinline__ void el_store_row(float* __restrict__ r, int d, const RgMap& q, float v0, const float (&vs)[4])
-{
-    if (q.live && q.sub == 0) r[0] = v0;
-    rg_store(r + 1, d, q, vs);
-}
-
 __global__ __launch_bounds__(EL_THREADS) void hm_el_bwd_kernel(const ElArgs a)
 {
     int gid, S;
-    const RgMap q = el_map(a, gid, S);
+    const RgMap q = rg_split_map(a.lsh, a.split, a.B, gid, S);
     const ElSample s = el_sample(a, q);
     const int d = a.d, d1 = a.d + 1, P = 1 + a.K;
     const int Pp = (P + S - 1) / S;
     RgMap qa = q;
     qa.live = s.ok;
-    const float* xr = a.x + (s.ok ? s.iu : 0) * a.ld;
-    float xs[4], acc[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-    const float x0 = s.ok ? xr[0] : 0.0f;
-    rg_load(xr + 1, d, qa, xs);
+    const RgRow x = rg_lrow_load(a.x + (s.ok ? s.iu : 0) * a.ld, d, qa, 0.0f);
+    RgRow acc = {0.0f, {0.0f, 0.0f, 0.0f, 0.0f}};              // the anchor's sum over this group's partners
     const float g = q.live ? a.gl[q.row] : 0.0f;
     const float* wr = a.w + q.row * (int64_t)P;
     const int64_t slot0 = q.row * (int64_t)(2 + a.K);
     const int64_t fill = s.ok ? s.iu : 0;                     // COO index of a skipped slot: its value row is zero
-    float acc0 = 0.0f;
     for (int i0 = 0; i0 < Pp; i0 += EL_FLIGHT) {
         int64_t idx[EL_FLIGHT];
         bool lv[EL_FLIGHT];
-        float ak[EL_FLIGHT], y0[EL_FLIGHT], ys[EL_FLIGHT][4];
+        float ak[EL_FLIGHT];
+        RgRow y[EL_FLIGHT];
 #pragma unroll
         for (int r = 0; r < EL_FLIGHT; ++r) {
             const int k = gid + S * (i0 + r);
             idx[r] = (s.ok && k < P) ? s.ix[1 + k] : -1;
-            lv[r] = el_in(idx[r], a.V);
-            ak[r] = lv[r] ? wr[k] : 0.0f;
+            ak[r] = rg_in(idx[r], a.V) ? wr[k] : 0.0f;
         }
-#pragma unroll
-        for (int r = 0; r < EL_FLIGHT; ++r) {
-            RgMap qk = q;
-            qk.live = lv[r];
-            const float* yr = a.x + (lv[r] ? idx[r] : 0) * a.ld;
-            y0[r] = lv[r] ? yr[0] : 0.0f;
-            rg_load(yr + 1, d, qk, ys[r]);
-        }
+        rg_gather<EL_FLIGHT>(a.x, a.ld, a.V, d, q, idx, 0.0f, lv, y);
 #pragma unroll
         for (int r = 0; r < EL_FLIGHT; ++r) {
             const int k = gid + S * (i0 + r);
             if (k >= P) continue;
-            acc0 = acc0 + ak[r] * y0[r];
-            float vs[4];
+            acc.t = acc.t + ak[r] * y[r].t;
+            RgRow v;
             const float ga = g * ak[r];
+            v.t = lv[r] ? ga * x.t : 0.0f;
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
-                acc[j] = acc[j] - ak[r] * ys[r][j];
-                vs[j] = lv[r] ? -(ga * xs[j]) : 0.0f;
+                acc.s[j] = acc.s[j] - ak[r] * y[r].s[j];
+                v.s[j] = lv[r] ? -(ga * x.s[j]) : 0.0f;
             }
-            el_store_row(a.val + (slot0 + 1 + k) * d1, d, q, lv[r] ? ga * x0 : 0.0f, vs);
+            rg_lrow_store(a.val + (slot0 + 1 + k) * d1, d, q, v);
             if (q.live && q.sub == 0) a.coo[slot0 + 1 + k] = lv[r] ? idx[r] : fill;
         }
     }
-    // form 1: the groups' partial sums of the anchor's gradient, lane by lane across the wave; group 0 stores the row
-    for (int off = 1 << a.lsh; off < (S << a.lsh); off <<= 1) {
-        acc0 = acc0 + __shfl_xor(acc0, off, 64);
+    rg_fold_groups(a.lsh, S, acc);                             // form 1: group 0 stores the anchor's row
+    RgRow v;
+    v.t = s.ok ? g * acc.t : 0.0f;
 #pragma unroll
-        for (int j = 0; j < 4; ++j) acc[j] = acc[j] + __shfl_xor(acc[j], off, 64);
-    }
-    float vs[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) vs[j] = s.ok ? g * acc[j] : 0.0f;
+    for (int j = 0; j < 4; ++j) v.s[j] = s.ok ? g * acc.s[j] : 0.0f;
     RgMap q0 = q;
     q0.live = q.live && gid == 0;
-    el_store_row(a.val + slot0 * d1, d, q0, s.ok ? g * acc0 : 0.0f, vs);
+    rg_lrow_store(a.val + slot0 * d1, d, q0, v);
     if (q0.live && q.sub == 0) a.coo[slot0] = fill;
 }
 
@@ -326,8 +287,8 @@ static int g_el_form = 1;
 static int el_args(const char* who, const float* x_dev, int64_t ld, int64_t V, int d1, const int64_t* index_dev, int64_t B, int64_t K,
                    float c, ElArgs& a)
 {
-    if (d1 < 2 || d1 > HM_RG_MAX_D + 1 || ld < d1 || V < 0 || V > ((int64_t)1 << 40) || B < 0 || B >= ((int64_t)1 << 31) || K < 0 ||
-        K > ((int64_t)1 << 20) || (B + 1) * (K + 2) > ((int64_t)1 << 40) || !(c > 0.0f) || !(c < INFINITY))
+    if (rg_bad_table(d1, ld, V) || B < 0 || B >= ((int64_t)1 << 31) || K < 0 || K > ((int64_t)1 << 20) ||
+        (B + 1) * (K + 2) > ((int64_t)1 << 40) || !(c > 0.0f) || !(c < INFINITY))
         return hm_fail(nullptr, HM_E_ARG, std::string(who) + ": bad arguments");
     if (!x_dev || !index_dev) return hm_fail(nullptr, HM_E_ARG, std::string(who) + ": NULL pointer");
     a = ElArgs{};
@@ -336,11 +297,6 @@ static int el_args(const char* who, const float* x_dev, int64_t ld, int64_t V, i
     a.K = (int)K; a.d = d1 - 1; a.lsh = rg_lsh(a.d); a.split = g_el_form;
     a.sqrt_c = sqrtf(c);
     return HM_OK;
-}
-
-static inline dim3 el_grid(const ElArgs& a)
-{
-    return dim3((unsigned)(a.split ? a.B : ((a.B << a.lsh) + EL_THREADS - 1) / EL_THREADS));
 }
 
 // Test / tuning hook: 0 = one lane group per sample, 1 = one wave per sample (the default), for the calls that follow.  The
@@ -360,7 +316,7 @@ extern "C" int hm_edge_loss_fwd(const float* x_dev, int64_t ld, int64_t table_ro
     if (!loss_dev || !weights_dev) return hm_fail(nullptr, HM_E_ARG, "hm_edge_loss_fwd: NULL pointer");
     if (n == 0) return HM_OK;
     a.loss = loss_dev; a.w = weights_dev;
-    hipLaunchKernelGGL(hm_el_fwd_kernel, el_grid(a), dim3(EL_THREADS), 0, (hipStream_t)stream, a);
+    hipLaunchKernelGGL(hm_el_fwd_kernel, rg_split_grid(a.B, a.lsh, a.split, EL_THREADS), dim3(EL_THREADS), 0, (hipStream_t)stream, a);
     HM_HIP0(hipGetLastError());
     return HM_OK;
 }
@@ -374,7 +330,7 @@ extern "C" int hm_edge_loss_bwd(const float* x_dev, int64_t ld, int64_t table_ro
     if (!weights_dev || !grad_loss_dev || !values_dev || !coo_dev) return hm_fail(nullptr, HM_E_ARG, "hm_edge_loss_bwd: NULL pointer");
     if (n == 0) return HM_OK;
     a.w = const_cast<float*>(weights_dev); a.gl = grad_loss_dev; a.val = values_dev; a.coo = coo_dev;
-    hipLaunchKernelGGL(hm_el_bwd_kernel, el_grid(a), dim3(EL_THREADS), 0, (hipStream_t)stream, a);
+    hipLaunchKernelGGL(hm_el_bwd_kernel, rg_split_grid(a.B, a.lsh, a.split, EL_THREADS), dim3(EL_THREADS), 0, (hipStream_t)stream, a);
     HM_HIP0(hipGetLastError());
     return HM_OK;
 }

@@ -2,9 +2,8 @@
 // vector-Jacobian products, engine-independent like the Lorentz row primitives of hm_lorentz.hip.
 //
 // Layout: the lane groups of hm_rowgroup.h, a group per row of width d <= 128.  The vector form is taken
-// when every operand allows it; the two conversions, whose Lorentz side starts one column in, take the scalar form.  Every
-// operand row is read once and every result row written once; the backward kernels recompute the row scalars from the
-// inputs.
+// when every operand allows it; the two conversions move Lorentz rows (RgRow).  Every operand row is read once and every
+// result row written once; the backward kernels recompute the row scalars from the inputs.
 //
 // The derivative is that of the reference's torch expression as torch differentiates it (clamp(min = 1e-8) passes the
 // gradient where the norm is >= 1e-8f, the (norm == 0) mask arithmetic is walked back term by term, norm' is 0 at the zero
@@ -233,11 +232,11 @@ __global__ __launch_bounds__(HM_RG_THREADS) void hm_pb_l2p_kernel(const float* _
                                                                   float* __restrict__ out, int64_t ldo)
 {
     const RgMap m = rg_map(lsh, 0, b);
-    float xs[4], o[4];
-    rg_load(x + m.row * ld + 1, d, m, xs);
-    const float den = (m.live ? x[m.row * ld] : 1.0f) + 1.0f / sc;
+    float o[4];
+    const RgRow xr = rg_lrow_load(x + m.row * ld, d, m, 1.0f);
+    const float den = xr.t + 1.0f / sc;
 #pragma unroll
-    for (int j = 0; j < 4; ++j) o[j] = xs[j] / den;
+    for (int j = 0; j < 4; ++j) o[j] = xr.s[j] / den;
     rg_store(out + m.row * ldo, d, m, o);
 }
 
@@ -246,16 +245,16 @@ __global__ __launch_bounds__(HM_RG_THREADS) void hm_pb_l2p_bwd_kernel(const floa
                                                                       float* __restrict__ gx, int64_t ldo)
 {
     const RgMap m = rg_map(lsh, 0, b);
-    float xs[4], gv[4], o[4];
-    rg_load(x + m.row * ld + 1, d, m, xs);
+    float gv[4];
+    const RgRow xr = rg_lrow_load(x + m.row * ld, d, m, 1.0f);
     rg_load(g + m.row * ldg, d, m, gv);
-    const float den = (m.live ? x[m.row * ld] : 1.0f) + 1.0f / sc;
+    const float den = xr.t + 1.0f / sc;
     const float dd = den * den;
-    const float g0 = rg_sum(m, ((-gv[0] * xs[0]) / dd + (-gv[1] * xs[1]) / dd) + ((-gv[2] * xs[2]) / dd + (-gv[3] * xs[3]) / dd));
+    RgRow o;
+    o.t = rg_sum(m, ((-gv[0] * xr.s[0]) / dd + (-gv[1] * xr.s[1]) / dd) + ((-gv[2] * xr.s[2]) / dd + (-gv[3] * xr.s[3]) / dd));
 #pragma unroll
-    for (int j = 0; j < 4; ++j) o[j] = gv[j] / den;
-    rg_store(gx + m.row * ldo + 1, d, m, o);
-    if (m.live && m.sub == 0) gx[m.row * ldo] = g0;
+    for (int j = 0; j < 4; ++j) o.s[j] = gv[j] / den;
+    rg_lrow_store(gx + m.row * ldo, d, m, o);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -266,15 +265,16 @@ __global__ __launch_bounds__(HM_RG_THREADS) void hm_pb_p2l_kernel(const float* _
                                                                   float ks, int lsh, float* __restrict__ out, int64_t ldo)
 {
     const RgMap m = rg_map(lsh, 0, b);
-    float xv[4], o[4];
+    float xv[4];
     rg_load(x + m.row * ld, d, m, xv);
     const float cx2 = c * rg_dot(m, xv, xv);
     const float f = 1.0f / (1.0f - cx2);
     const float kf = ks * f;
+    RgRow o;
+    o.t = (f * (1.0f + cx2)) / k0;
 #pragma unroll
-    for (int j = 0; j < 4; ++j) o[j] = kf * xv[j];
-    rg_store(out + m.row * ldo + 1, d, m, o);
-    if (m.live && m.sub == 0) out[m.row * ldo] = (f * (1.0f + cx2)) / k0;
+    for (int j = 0; j < 4; ++j) o.s[j] = kf * xv[j];
+    rg_lrow_store(out + m.row * ldo, d, m, o);
 }
 
 __global__ __launch_bounds__(HM_RG_THREADS) void hm_pb_p2l_bwd_kernel(const float* __restrict__ x, const float* __restrict__ g, int64_t ldg,
@@ -282,18 +282,17 @@ __global__ __launch_bounds__(HM_RG_THREADS) void hm_pb_p2l_bwd_kernel(const floa
                                                                       float* __restrict__ gx, int64_t ldo)
 {
     const RgMap m = rg_map(lsh, 0, b);
-    float xv[4], gs[4], o[4];
+    float xv[4], o[4];
     rg_load(x + m.row * ld, d, m, xv);
-    rg_load(g + m.row * ldg + 1, d, m, gs);
-    const float g0 = m.live ? g[m.row * ldg] : 0.0f;
+    const RgRow gr = rg_lrow_load(g + m.row * ldg, d, m, 0.0f);
     const float cx2 = c * rg_dot(m, xv, xv);
     const float f = 1.0f / (1.0f - cx2);
     const float kf = ks * f;
-    const float gf = (g0 * (1.0f + cx2)) / k0 + ks * rg_dot(m, gs, xv);
-    const float gh = (g0 * f) / k0;                           // towards 1 + c |x|^2
+    const float gf = (gr.t * (1.0f + cx2)) / k0 + ks * rg_dot(m, gr.s, xv);
+    const float gh = (gr.t * f) / k0;                         // towards 1 + c |x|^2
     const float gx2 = c * gh + c * ((gf * f) * f);            // 1 / den: -grad * result^2, den = 1 - c |x|^2
 #pragma unroll
-    for (int j = 0; j < 4; ++j) o[j] = gs[j] * kf + (2.0f * gx2) * xv[j];
+    for (int j = 0; j < 4; ++j) o[j] = gr.s[j] * kf + (2.0f * gx2) * xv[j];
     rg_store(gx + m.row * ldo, d, m, o);
 }
 

@@ -13,14 +13,13 @@
 //   table gradient: position t of segment i -> COO index ids[t], value row w_t h_i;  dL/dw_t = h_i . x_{ids[t]}
 //   a skipped position (slack, id outside [0, V), outside every span): index 0, zero value row, zero weight gradient
 //
-// Layout: the lane groups of hm_rowgroup.h, 16 (d <= 64) or 32 lanes per row, scalar form (the spatial part starts one column
-// into the row), the time column a per-row scalar beside the slots as in hm_riemann.hip.  A block is one wave.  Two forms
-// (hm_debug_centroid_form):
-//   form 0  one GROUP per segment (4 or 2 segments per wave): the group walks all tokens of its segment;
-//   form 1  one WAVE per segment: its S = 4 or 2 groups take the tokens g, g + S, g + 2 S, ... and combine s by butterflies.
-// A walk keeps PL_FLIGHT token rows in flight per group: the ids and weights of a round are loaded before its rows, the rows
-// before the first is used.  Trip counts are made uniform over the wave (the longest walk of its groups); a group whose
-// segment has ended runs the remaining rounds with every access predicated off.
+// Layout: Lorentz rows gathered on the lane groups of hm_rowgroup.h.  Two forms (hm_debug_centroid_form,
+// rg_split_map):
+//   form 0  one GROUP per segment: the group walks all tokens of its segment;
+//   form 1  one WAVE per segment: its S groups take the tokens g, g + S, g + 2 S, ... and combine s by rg_fold_groups.
+// A walk goes in flights of PL_FLIGHT token rows per group (rg_gather's): the ids and weights of a round are loaded before its
+// rows.  Trip counts are made uniform over the wave (the longest walk of its groups); a group whose segment has ended runs
+// the remaining rounds with every access predicated off.
 //   forward   s_i stays in registers; writes mu_i and 1 / nu_i.
 //   backward  forms h_i once per segment, then walks the span [offsets[i], offsets[i + 1]) -- segment 0 from position 0 and
 //             segment n - 1 up to T, so that one launch covers [0, T) -- and writes every value row and every COO index
@@ -29,7 +28,7 @@
 
 #pragma clang fp contract(off)
 
-#define PL_THREADS 64                                         // one wave per block: 4 or 2 segments (form 0) or one (form 1)
+#define PL_THREADS HM_RG_WAVE                                 // one wave per block: 4 or 2 segments (form 0) or one (form 1)
 #define PL_FLIGHT 4                                           // token rows in flight per group
 
 struct PlArgs {
@@ -47,27 +46,6 @@ struct PlArgs {
     int64_t ld, n, V, T;
     int d, lsh, split;
 };
-
-__device__ __forceinline__ bool pl_in(int64_t i, int64_t V) { return i >= 0 && i < V; }
-
-// lane -> (segment, group of the segment, lane of the group)
-__device__ __forceinline__ RgMap pl_map(const PlArgs& a, int& gid, int& S)
-{
-    if (!a.split) {
-        gid = 0;
-        S = 1;
-        return rg_map(a.lsh, 0, a.n);
-    }
-    RgMap m;
-    m.lsh = a.lsh;
-    m.vec = 0;
-    m.sub = (int)(threadIdx.x & ((1u << a.lsh) - 1u));
-    m.row = (int64_t)blockIdx.x;
-    m.live = m.row < a.n;
-    gid = (int)(threadIdx.x >> a.lsh);
-    S = PL_THREADS >> a.lsh;
-    return m;
-}
 
 // the positions of a segment: the live tokens are [b, e), the backward's walk covers [lo, hi); all inside [0, T]
 struct PlSeg {
@@ -116,15 +94,16 @@ __device__ __forceinline__ double pl_sum_d(const RgMap& m, double a)
 __global__ __launch_bounds__(PL_THREADS) void hm_pl_fwd_kernel(const PlArgs a)
 {
     int gid, S;
-    const RgMap q = pl_map(a, gid, S);
+    const RgMap q = rg_split_map(a.lsh, a.split, a.n, gid, S);
     const PlSeg sg = pl_seg(a, q);
     const int d = a.d;
     const int64_t rounds = pl_rounds(sg.e - sg.b, gid, S);
-    float s0 = 0.0f, ss[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+    RgRow s = {0.0f, {0.0f, 0.0f, 0.0f, 0.0f}};
     for (int64_t i0 = 0; i0 < rounds; i0 += PL_FLIGHT) {
         int64_t idx[PL_FLIGHT];
         bool lv[PL_FLIGHT];
-        float wt[PL_FLIGHT], y0[PL_FLIGHT], ys[PL_FLIGHT][4];
+        float wt[PL_FLIGHT];
+        RgRow y[PL_FLIGHT];
 #pragma unroll
         for (int r = 0; r < PL_FLIGHT; ++r) {
             const int64_t p = sg.b + gid + S * (i0 + r);
@@ -132,56 +111,43 @@ __global__ __launch_bounds__(PL_THREADS) void hm_pl_fwd_kernel(const PlArgs a)
             idx[r] = in ? a.ids[p] : -1;
             wt[r] = (in && a.w) ? a.w[p] : 1.0f;
         }
-#pragma unroll
-        for (int r = 0; r < PL_FLIGHT; ++r) {
-            lv[r] = pl_in(idx[r], a.V);
-            RgMap qk = q;
-            qk.live = lv[r];
-            const float* yr = a.x + (lv[r] ? idx[r] : 0) * a.ld;
-            y0[r] = lv[r] ? yr[0] : 0.0f;
-            rg_load(yr + 1, d, qk, ys[r]);
-        }
+        rg_gather<PL_FLIGHT>(a.x, a.ld, a.V, d, q, idx, 0.0f, lv, y);
 #pragma unroll
         for (int r = 0; r < PL_FLIGHT; ++r) {
             const float w = lv[r] ? wt[r] : 0.0f;             // a skipped token adds w x = 0 * 0
-            s0 = fmaf(w, y0[r], s0);
+            s.t = fmaf(w, y[r].t, s.t);
 #pragma unroll
-            for (int j = 0; j < 4; ++j) ss[j] = fmaf(w, ys[r][j], ss[j]);
+            for (int j = 0; j < 4; ++j) s.s[j] = fmaf(w, y[r].s[j], s.s[j]);
         }
     }
-    // form 1: the groups' partial sums, lane by lane across the wave
-    for (int off = 1 << a.lsh; off < (S << a.lsh); off <<= 1) {
-        s0 = s0 + __shfl_xor(s0, off, 64);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) ss[j] = ss[j] + __shfl_xor(ss[j], off, 64);
-    }
+    rg_fold_groups(a.lsh, S, s);                              // form 1: every group ends with the segment's sum
     double sq = 0.0;
 #pragma unroll
-    for (int j = 0; j < 4; ++j) sq = sq + (double)ss[j] * (double)ss[j];
+    for (int j = 0; j < 4; ++j) sq = sq + (double)s.s[j] * (double)s.s[j];
     sq = pl_sum_d(q, sq);
-    const double qq = (double)s0 * (double)s0 - sq;
+    const double qq = (double)s.t * (double)s.t - sq;
     const bool ok = qq > 0.0 && qq < (double)INFINITY;        // false for NaN as well
     const double nu = __builtin_sqrt(ok ? qq : 1.0);
-    float ms[4];
+    RgRow m;
+    m.t = ok ? (float)((double)s.t / nu) : 1.0f;
 #pragma unroll
-    for (int j = 0; j < 4; ++j) ms[j] = ok ? (float)((double)ss[j] / nu) : 0.0f;
+    for (int j = 0; j < 4; ++j) m.s[j] = ok ? (float)((double)s.s[j] / nu) : 0.0f;
     RgMap q0 = q;
     q0.live = q.live && gid == 0;
-    float* mr = a.mu + q.row * (int64_t)(d + 1);
-    if (q0.live && q.sub == 0) {
-        mr[0] = ok ? (float)((double)s0 / nu) : 1.0f;
-        a.inv[q.row] = ok ? (float)(1.0 / nu) : 0.0f;
-    }
-    rg_store(mr + 1, d, q0, ms);
+    if (q0.live && q.sub == 0) a.inv[q.row] = ok ? (float)(1.0 / nu) : 0.0f;
+    rg_lrow_store(a.mu + q.row * (int64_t)(d + 1), d, q0, m);
 }
 
 template <bool GW>
 __global__ __launch_bounds__(PL_THREADS) void hm_pl_bwd_kernel(const PlArgs a)
 {
     int gid, S;
-    const RgMap q = pl_map(a, gid, S);
+    const RgMap q = rg_split_map(a.lsh, a.split, a.n, gid, S);
     const PlSeg sg = pl_seg(a, q);
     const int d = a.d, d1 = a.d + 1;
+    // The rows of this kernel are written out, not RgRow / rg_gather / rg_lrow_store: a position's time column and COO index
+    // go under ONE exec mask (two `if`s on the same lane stay two divergent regions in the machine code, 1 - 2 % of the
+    // kernel), and the table rows are gathered only for the weight gradient.
     // h_i, on every lane of every group of the segment
     const float* gr = a.g + q.row * (int64_t)d1;
     const float* mr = a.mu + q.row * (int64_t)d1;
@@ -218,7 +184,7 @@ __global__ __launch_bounds__(PL_THREADS) void hm_pl_bwd_kernel(const PlArgs a)
         }
 #pragma unroll
         for (int r = 0; r < PL_FLIGHT; ++r) {
-            lv[r] = pl_in(idx[r], a.V);
+            lv[r] = rg_in(idx[r], a.V);
             if (GW) {
                 RgMap qk = q;
                 qk.live = lv[r];
@@ -270,8 +236,7 @@ static int pl_args(const char* who, const float* x_dev, int64_t ld, int64_t V, i
                    const int64_t* offsets_dev, const int32_t* lengths_dev, const float* weights_dev, int64_t n, PlArgs& a)
 {
     if (!x_dev) return hm_fail(nullptr, HM_E_ARG, std::string(who) + ": NULL table");
-    if (d1 < 2 || d1 > HM_RG_MAX_D + 1 || ld < d1 || V < 0 || V > ((int64_t)1 << 40) || n < 0 || n >= ((int64_t)1 << 31) || t < 0 ||
-        t > ((int64_t)1 << 40))
+    if (rg_bad_table(d1, ld, V) || n < 0 || n >= ((int64_t)1 << 31) || t < 0 || t > ((int64_t)1 << 40))
         return hm_fail(nullptr, HM_E_ARG, std::string(who) + ": bad arguments");
     if ((n > 0 && !offsets_dev) || (t > 0 && !ids_dev)) return hm_fail(nullptr, HM_E_ARG, std::string(who) + ": NULL pointer");
     a = PlArgs{};
@@ -280,11 +245,6 @@ static int pl_args(const char* who, const float* x_dev, int64_t ld, int64_t V, i
     a.d = d1 - 1; a.lsh = rg_lsh(a.d);
     a.split = g_pl_form >= 0 ? g_pl_form : pl_auto_form(n, t, a.lsh);
     return HM_OK;
-}
-
-static inline dim3 pl_grid(const PlArgs& a)
-{
-    return dim3((unsigned)(a.split ? a.n : ((a.n << a.lsh) + PL_THREADS - 1) / PL_THREADS));
 }
 
 // Test / tuning hook: 0 = one lane group per segment, 1 = one wave per segment, -1 = chosen per call from n and the mean
@@ -305,7 +265,7 @@ extern "C" int hm_centroid_fwd(const float* x_dev, int64_t ld, int64_t table_row
     if (n == 0) return HM_OK;
     if (!mu_dev || !inv_nu_dev) return hm_fail(nullptr, HM_E_ARG, "hm_centroid_fwd: NULL pointer");
     a.mu = mu_dev; a.inv = inv_nu_dev;
-    hipLaunchKernelGGL(hm_pl_fwd_kernel, pl_grid(a), dim3(PL_THREADS), 0, (hipStream_t)stream, a);
+    hipLaunchKernelGGL(hm_pl_fwd_kernel, rg_split_grid(n, a.lsh, a.split, PL_THREADS), dim3(PL_THREADS), 0, (hipStream_t)stream, a);
     HM_HIP0(hipGetLastError());
     return HM_OK;
 }
@@ -328,10 +288,11 @@ extern "C" int hm_centroid_bwd(const float* x_dev, int64_t ld, int64_t table_row
     if (!mu_dev || !inv_nu_dev || !grad_dev) return hm_fail(nullptr, HM_E_ARG, "hm_centroid_bwd: NULL pointer");
     a.mu = const_cast<float*>(mu_dev); a.inv = const_cast<float*>(inv_nu_dev); a.g = grad_dev;
     a.val = values_dev; a.coo = coo_dev; a.gw = grad_weights_dev;
+    const dim3 grid = rg_split_grid(n, a.lsh, a.split, PL_THREADS);
     if (grad_weights_dev)
-        hipLaunchKernelGGL(hm_pl_bwd_kernel<true>, pl_grid(a), dim3(PL_THREADS), 0, (hipStream_t)stream, a);
+        hipLaunchKernelGGL(hm_pl_bwd_kernel<true>, grid, dim3(PL_THREADS), 0, (hipStream_t)stream, a);
     else
-        hipLaunchKernelGGL(hm_pl_bwd_kernel<false>, pl_grid(a), dim3(PL_THREADS), 0, (hipStream_t)stream, a);
+        hipLaunchKernelGGL(hm_pl_bwd_kernel<false>, grid, dim3(PL_THREADS), 0, (hipStream_t)stream, a);
     HM_HIP0(hipGetLastError());
     return HM_OK;
 }

@@ -1,11 +1,9 @@
 // hm_riemann.hip -- one fused, in-place Riemannian optimiser step (RSGD, Riemannian Adam) for rows on the unit
 // hyperboloid <x, x> = -1, <a, b> = -a0 b0 + sum_k ak bk; engine-independent like the hm_rows_* kernels.
 //
-// Layout: the lane groups of hm_rowgroup.h, a group per row of spatial width d = d1 - 1 <= 128, always in
-// the scalar form (the spatial part starts one column into the row, so no 16-byte form exists for it).  The time coordinate
-// of x, g and m is a per-row scalar every lane of the group carries beside its slots.  Every operand row is read once and
-// every result row written once, in place; a group lives inside one wave, whose loads of a row all precede its stores in
-// program order.  No atomics, no LDS, no workspace.
+// Layout: the Lorentz rows of hm_rowgroup.h, a lane group per row of d1 <= 129 columns.  Every operand row
+// is read once and every result row written once, in place; a group lives inside one wave, whose loads of a row all precede
+// its stores in program order.  No atomics, no LDS, no workspace.
 //
 // The step (formulas fixed by DESIGN.md 5.16, not by lorentz_model.exp_map / parallel_transport / riemannian_gradient):
 //   u  = h + <x, h> x, h = (-g0, g1, ...)                               Riemannian gradient
@@ -34,18 +32,8 @@ struct RoArgs {
     float b2, omb2, eps, bc1, bc2;
 };
 
-// column 0 of a Lorentz row beside its slots: read by every lane of a live group, written by the group's first lane
-__device__ __forceinline__ float ro_time(const float* __restrict__ r, const RgMap& q, float dead0) { return q.live ? r[0] : dead0; }
-__device__ __forceinline__ void ro_set_time(float* __restrict__ r, const RgMap& q, float v0)
-{
-    if (q.live && q.sub == 0) r[0] = v0;
-}
-
 // <a, b> = -a0 b0 + sum_k ak bk
-__device__ __forceinline__ float ro_ldot(const RgMap& m, float a0, const float (&a)[4], float b0, const float (&b)[4])
-{
-    return rg_dot(m, a, b) - a0 * b0;
-}
+__device__ __forceinline__ float ro_ldot(const RgMap& m, const RgRow& a, const RgRow& b) { return rg_dot(m, a.s, b.s) - a.t * b.t; }
 
 template <int OPT>
 __global__ __launch_bounds__(HM_RG_THREADS) void hm_ro_step_kernel(const RoArgs a)
@@ -57,93 +45,80 @@ __global__ __launch_bounds__(HM_RG_THREADS) void hm_ro_step_kernel(const RoArgs 
     int64_t row = t;
     if (q.live && a.rows) {
         row = a.rows[t];
-        q.live = row >= 0 && row < a.table_rows;
+        q.live = rg_in(row, a.table_rows);
     }
     const int d = a.d;
     float* xr = a.x + row * a.ld_x;
-    const float* gr = a.g + t * a.ld_g;
     float* mr = a.m + row * a.ld_m;
-    float xs[4], gs[4], ms[4], us[4], ss[4], ys[4], ws[4];
-    const float x0 = ro_time(xr, q, 1.0f);                    // dead rows keep the origin
-    rg_load(xr + 1, d, q, xs);
-    const float g0 = ro_time(gr, q, 0.0f);
-    rg_load(gr + 1, d, q, gs);
-    float m0 = 0.0f, vv = 0.0f;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) ms[j] = 0.0f;
-    if (OPT != HM_RO_SGD) {
-        m0 = ro_time(mr, q, 0.0f);
-        rg_load(mr + 1, d, q, ms);
-    }
+    const RgRow x = rg_lrow_load(xr, d, q, 1.0f);             // dead rows keep the origin
+    const RgRow g = rg_lrow_load(a.g + t * a.ld_g, d, q, 0.0f);
+    RgRow m = {0.0f, {0.0f, 0.0f, 0.0f, 0.0f}}, h = g, u, s, y, w;
+    float vv = 0.0f;
+    if (OPT != HM_RO_SGD) m = rg_lrow_load(mr, d, q, 0.0f);
     if (OPT == HM_RO_ADAM && q.live) vv = a.v[row];
 
     // Riemannian gradient: h = (-g0, g_s), u = h + <x, h> x
-    const float h0 = -g0;
-    const float xh = ro_ldot(q, x0, xs, h0, gs);
-    const float u0 = h0 + xh * x0;
+    h.t = -g.t;
+    const float xh = ro_ldot(q, x, h);
+    u.t = h.t + xh * x.t;
 #pragma unroll
-    for (int j = 0; j < 4; ++j) us[j] = gs[j] + xh * xs[j];
+    for (int j = 0; j < 4; ++j) u.s[j] = h.s[j] + xh * x.s[j];
 
     // moments and direction; s = -lr dir
-    float s0;
     if (OPT == HM_RO_SGD) {
-        m0 = u0;
+        m = u;
+        s.t = -a.lr * u.t;
 #pragma unroll
-        for (int j = 0; j < 4; ++j) ms[j] = us[j];
-        s0 = -a.lr * u0;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) ss[j] = -a.lr * us[j];
+        for (int j = 0; j < 4; ++j) s.s[j] = -a.lr * u.s[j];
     } else if (OPT == HM_RO_SGD_MOM) {
-        m0 = a.k_m * m0 + a.k_u * u0;
+        m.t = a.k_m * m.t + a.k_u * u.t;
 #pragma unroll
-        for (int j = 0; j < 4; ++j) ms[j] = a.k_m * ms[j] + a.k_u * us[j];
+        for (int j = 0; j < 4; ++j) m.s[j] = a.k_m * m.s[j] + a.k_u * u.s[j];
         if (a.nesterov) {
-            s0 = -a.lr * (u0 + a.k_m * m0);
+            s.t = -a.lr * (u.t + a.k_m * m.t);
 #pragma unroll
-            for (int j = 0; j < 4; ++j) ss[j] = -a.lr * (us[j] + a.k_m * ms[j]);
+            for (int j = 0; j < 4; ++j) s.s[j] = -a.lr * (u.s[j] + a.k_m * m.s[j]);
         } else {
-            s0 = -a.lr * m0;
+            s.t = -a.lr * m.t;
 #pragma unroll
-            for (int j = 0; j < 4; ++j) ss[j] = -a.lr * ms[j];
+            for (int j = 0; j < 4; ++j) s.s[j] = -a.lr * m.s[j];
         }
     } else {
-        m0 = a.k_m * m0 + a.k_u * u0;
+        m.t = a.k_m * m.t + a.k_u * u.t;
 #pragma unroll
-        for (int j = 0; j < 4; ++j) ms[j] = a.k_m * ms[j] + a.k_u * us[j];
-        const float uu = ro_ldot(q, u0, us, u0, us);          // the row's squared Riemannian norm
+        for (int j = 0; j < 4; ++j) m.s[j] = a.k_m * m.s[j] + a.k_u * u.s[j];
+        const float uu = ro_ldot(q, u, u);                    // the row's squared Riemannian norm
         vv = a.b2 * vv + a.omb2 * uu;
         const float den = __builtin_sqrtf(vv / a.bc2) + a.eps;
-        s0 = -a.lr * ((m0 / a.bc1) / den);
+        s.t = -a.lr * ((m.t / a.bc1) / den);
 #pragma unroll
-        for (int j = 0; j < 4; ++j) ss[j] = -a.lr * ((ms[j] / a.bc1) / den);
+        for (int j = 0; j < 4; ++j) s.s[j] = -a.lr * ((m.s[j] / a.bc1) / den);
     }
 
     // retraction: Exp_x(s), then the time coordinate from the spatial part
-    const float n2 = ro_ldot(q, s0, ss, s0, ss);
+    const float n2 = ro_ldot(q, s, s);
     const float nn = __builtin_sqrtf((n2 < 0.0f) ? 0.0f : n2);   // NaN propagates
     float ch, sh;
     hm::cosh_sinh_c(nn, ch, sh);
     const float coef = (nn > 0.0f) ? sh / nn : 1.0f;
 #pragma unroll
-    for (int j = 0; j < 4; ++j) ys[j] = ch * xs[j] + coef * ss[j];
-    const float y0 = __builtin_sqrtf(1.0f + rg_dot(q, ys, ys));
-    rg_store(xr + 1, d, q, ys);
-    ro_set_time(xr, q, y0);
+    for (int j = 0; j < 4; ++j) y.s[j] = ch * x.s[j] + coef * s.s[j];
+    y.t = __builtin_sqrtf(1.0f + rg_dot(q, y.s, y.s));
+    rg_lrow_store(xr, d, q, y);
     if (OPT == HM_RO_SGD) return;
 
     // transport of m+ from x to y, re-projected onto the tangent space at y
-    const float ym = ro_ldot(q, y0, ys, m0, ms);
-    const float xy = ro_ldot(q, x0, xs, y0, ys);
+    const float ym = ro_ldot(q, y, m);
+    const float xy = ro_ldot(q, x, y);
     const float f = ym / (1.0f - xy);
-    const float w0 = m0 + f * (x0 + y0);
+    w.t = m.t + f * (x.t + y.t);
 #pragma unroll
-    for (int j = 0; j < 4; ++j) ws[j] = ms[j] + f * (xs[j] + ys[j]);
-    const float yw = ro_ldot(q, y0, ys, w0, ws);
-    const float o0 = w0 + yw * y0;
+    for (int j = 0; j < 4; ++j) w.s[j] = m.s[j] + f * (x.s[j] + y.s[j]);
+    const float yw = ro_ldot(q, y, w);
+    w.t = w.t + yw * y.t;
 #pragma unroll
-    for (int j = 0; j < 4; ++j) ws[j] = ws[j] + yw * ys[j];
-    rg_store(mr + 1, d, q, ws);
-    ro_set_time(mr, q, o0);
+    for (int j = 0; j < 4; ++j) w.s[j] = w.s[j] + yw * y.s[j];
+    rg_lrow_store(mr, d, q, w);
     if (OPT == HM_RO_ADAM && q.live && q.sub == 0) a.v[row] = vv;
 }
 
@@ -153,7 +128,7 @@ __global__ __launch_bounds__(HM_RG_THREADS) void hm_ro_step_kernel(const RoArgs 
 static inline bool ro_unit(float b) { return b >= 0.0f && b < 1.0f; }            // false for NaN
 static inline bool ro_bad_common(int64_t ld_x, int64_t ld_g, int64_t n, int64_t table_rows, int d1, float lr, bool dense)
 {
-    if (d1 < 2 || d1 > HM_RG_MAX_D + 1 || ld_x < d1 || ld_g < d1) return true;
+    if (rg_bad_lrow(d1, ld_x) || ld_g < d1) return true;
     if (n < 0 || n > ((int64_t)1 << 31) || table_rows < 0 || (dense && n != table_rows)) return true;
     return !(lr >= 0.0f) || !(lr < INFINITY);
 }
