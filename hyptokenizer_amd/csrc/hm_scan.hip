@@ -95,14 +95,21 @@ __device__ __forceinline__ void hm_dma_run(const char* src, uint32_t dst)
 // asynchronous key load is picked up DIST - 1 tiles after it went out (vector-memory loads return in order: by then the
 // wait of that tile has passed the tile requested right behind it); and the queue draw is picked up behind the run's
 // closing vmcnt(0).
-template <int NG, int SIGN, int MODE, int BF, int TM, int WPB, int SUB, bool WK = false, int HEAD = 0, int RING = 0>
+//
+// SPAN = 2 (head kernels on rings 1 and 2; ScanRun of hm_scan_geom.h): two ring slots -- four groups, one pipeline -- between
+// two barriers.  The slots keep their place in the ring and a failed group is still recomputed from the slot it sits in, in
+// front of the barrier that frees it; what changes is the grain of everything paid per barrier: one request of two slots,
+// one counted wait, one fresh group and one reduction outside the MFMAs' shadow per 128 columns, and for tiles right of
+// the block's rows a straight-line body (head_tile_lean).  The key load of a tile is picked up behind that tile's own wait.
+template <int NG, int SIGN, int MODE, int BF, int TM, int WPB, int SUB, bool WK = false, int HEAD = 0, int RING = 0, int SPAN = 1>
 __global__ __launch_bounds__(64 * WPB, 2) void hm_scan_kernel(const ScanArgs p)
 {
     static_assert(SUB % 2 == 0, "the two accumulator sets alternate between column groups: an even number per tile");
     static_assert(RING == 0 || HEAD > 0, "rings other than 0 belong to the head kernels");
     constexpr bool PIPE = (TM <= HM_SCAN_PIPE_MAX_TM);   // two accumulator sets fit the registers (128 stationary rows per wave: one set)
     // the geometry of this instantiation (hm_scan_geom.h: sizes, ring, LDS map)
-    using G = ScanGeom<NG, BF, TM, WPB, SUB, RING>;
+    using G = ScanGeom<NG, BF, TM, WPB, SUB, RING, SPAN>;
+    static_assert(G::SPAN == SPAN, "a span the ring has no slots for is the dispatch's to replace (hm_launch_scan_ng)");
     constexpr int COLS = G::COLS, RS = G::RS, RB16 = G::RB16, TILE_BYTES = G::TILE_BYTES, NP = G::NP;
     constexpr int PPW = G::PPW, TILE_LDS = G::TILE_LDS, DIST = G::DIST, NBUF = G::NBUF;
     constexpr int RSUB = G::RSUB;                  // 32-column groups per ring slot (SUB: per tile of the item plan)
@@ -525,12 +532,13 @@ __global__ __launch_bounds__(64 * WPB, 2) void hm_scan_kernel(const ScanArgs p)
     // bfr[set] before the MFMAs start (requested by the previous group unless `fresh`), the next group's go out to
     // bfr[set ^ 1] behind the first k-step, and with RED the reduction of the other set -- the head values of the group
     // before -- rides in the issue shadow of the MFMAs; its result goes to `ext`
-    auto head_group = [&](auto set_c, auto red_c, int buf, int sub, bool fresh, float& ext) __attribute__((always_inline)) {
+    // `bt`: the lane's row of the group in its ring slot (head_at); `btn`: of the group whose fragments go out (NEXT)
+    auto head_at = [&](int buf, int sub) __attribute__((always_inline)) -> const char* { return smem + buf * TILE_LDS + (sub * 32 + r) * RB16 + 16 * h; };
+    auto head_group = [&](auto set_c, auto red_c, auto next_c, const char* bt, const char* btn, bool fresh, float& ext) __attribute__((always_inline)) {
         constexpr int set = decltype(set_c)::value;
-        constexpr bool RED = decltype(red_c)::value;
+        constexpr bool RED = decltype(red_c)::value, NEXT = decltype(next_c)::value;
         constexpr int QN = 16 * TM;
         if constexpr (HEAD > 0) {
-            const char* bt = smem + buf * TILE_LDS + (sub * 32 + r) * RB16 + 16 * h;
             if (fresh) {
 #pragma unroll
                 for (int k = 0; k < HEAD; ++k) bfr[set][k] = frag_at(bt, hm_head_kstep(k, NP));
@@ -558,10 +566,12 @@ __global__ __launch_bounds__(64 * WPB, 2) void hm_scan_kernel(const ScanArgs p)
             };
             kstep(std::integral_constant<int, 0>{});
             __builtin_amdgcn_sched_barrier(0);
-            // unconditional, like mma_group_deep's: behind the last group of a tile the addresses fall into the next slot or
-            // the slack behind the ring and the data is never used
+            // no run-time condition, like mma_group_deep's: behind the last group of a slot of the span-1 walk the addresses
+            // fall into the next slot or the slack behind the ring and the data is never used
+            if constexpr (NEXT) {
 #pragma unroll
-            for (int k = 0; k < HEAD; ++k) bfr[set ^ 1][k] = frag_at(bt + 32 * RB16, hm_head_kstep(k, NP));
+                for (int k = 0; k < HEAD; ++k) bfr[set ^ 1][k] = frag_at(btn, hm_head_kstep(k, NP));
+            }
             __builtin_amdgcn_sched_barrier(0);
             static_assert(HEAD <= 4, "the head k-steps are written out");
             if constexpr (HEAD > 1) kstep(std::integral_constant<int, 1>{});
@@ -620,6 +630,107 @@ __global__ __launch_bounds__(64 * WPB, 2) void hm_scan_kernel(const ScanArgs p)
         return false;
     };
 
+    // RING > 0: the counted wait that leaves the pieces of at most `tiles` (wave-uniform; WMAX at most count) of this wave's
+    // ring slots outstanding; a key load or a queue draw among the outstanding only makes the count stricter
+    constexpr int WMAX = ScanRun::outstanding_max(NBUF, SPAN);
+    auto ring_wait = [&](int tiles) __attribute__((always_inline)) {
+        auto wait_p = [&](auto p_c) __attribute__((always_inline)) {
+            constexpr int P = decltype(p_c)::value;
+            static_assert(WMAX * P <= 60, "the counted wait must fit vmcnt");
+            if (tiles >= 3 && WMAX >= 3) asm volatile("s_waitcnt vmcnt(%0)" : : "n"(3 * P) : "memory");
+            else if (tiles >= 2 && WMAX >= 2) asm volatile("s_waitcnt vmcnt(%0)" : : "n"(2 * P) : "memory");
+            else if (tiles >= 1 && WMAX >= 1) asm volatile("s_waitcnt vmcnt(%0)" : : "n"(P) : "memory");
+            else asm volatile("s_waitcnt vmcnt(0)" : : : "memory");
+        };
+        static_assert(RING == 0 || WMAX <= 3, "ring_wait writes out the depths");
+        if constexpr (PREM != 0) {
+            if (wave < PREM) wait_p(std::integral_constant<int, PQ + 1>{});
+            else wait_p(std::integral_constant<int, PQ>{});
+        } else {
+            wait_p(std::integral_constant<int, G::EXACT ? PQ : PPW>{});
+        }
+    };
+
+    // head walk of the ring slot `buf` (columns from j0 on): its groups alternate between the accumulator sets; group g's
+    // head k-steps carry the reduction of group g - 1's head values, whose test follows.  Nothing is pending behind the slot
+    // (the recomputation of a failed group reads its columns from the slot): the last group is reduced on its own.
+    auto head_walk = [&](int buf, int j0) __attribute__((always_inline)) {
+        if constexpr (HEAD > 0) {
+            bool hp = false;
+            int hg = 0, hc = 0;          // groups of this slot that ran / that had to be recomputed
+#pragma unroll 1
+            for (int sp = 0; sp < RSUB / 2; ++sp) {
+                {
+                    const int sub = 2 * sp;
+                    const int j0s = j0 + sub * 32;
+                    const bool do_c = wave_active && (j0s + 31 > i0w);
+                    const char* bt = head_at(buf, sub);
+                    float ext_u = 0.0f;
+                    if (do_c && hp) {
+                        head_group(std::integral_constant<int, 0>{}, std::true_type{}, std::true_type{}, bt, bt + 32 * RB16, false, ext_u);
+                    } else {
+                        if (do_c) head_group(std::integral_constant<int, 0>{}, std::false_type{}, std::true_type{}, bt, bt + 32 * RB16, true, ext_u);
+                        if (hp) ext_u = reduce_group(std::integral_constant<int, 1>{});
+                    }
+                    if (hp) { ++hg; hc += head_finish(std::integral_constant<int, 1>{}, ext_u, buf, sub - 1, j0s - 32) ? 1 : 0; }
+                    hp = do_c;
+                }
+                {
+                    const int sub = 2 * sp + 1;
+                    const int j0s = j0 + sub * 32;
+                    const bool do_c = wave_active && (j0s + 31 > i0w);
+                    const char* bt = head_at(buf, sub);
+                    float ext_u = 0.0f;
+                    if (do_c && hp) {
+                        head_group(std::integral_constant<int, 1>{}, std::true_type{}, std::true_type{}, bt, bt + 32 * RB16, false, ext_u);
+                    } else {
+                        if (do_c) head_group(std::integral_constant<int, 1>{}, std::false_type{}, std::true_type{}, bt, bt + 32 * RB16, true, ext_u);
+                        if (hp) ext_u = reduce_group(std::integral_constant<int, 0>{});
+                    }
+                    if (hp) { ++hg; hc += head_finish(std::integral_constant<int, 0>{}, ext_u, buf, sub - 1, j0s - 32) ? 1 : 0; }
+                    hp = do_c;
+                }
+            }
+            if (hp) { ++hg; hc += head_finish(std::integral_constant<int, 1>{}, reduce_group(std::integral_constant<int, 1>{}), buf, RSUB - 1, j0 + (RSUB - 1) * 32) ? 1 : 0; }
+            hg_tot += hg; hc_tot += hc;
+        }
+    };
+
+    // the interior tile of the span-2 walk (SPAN = 2): the four groups of the two slots `buf0`, `buf1` (columns from j0 on,
+    // all of them right of the block's rows, on an active wave) as one pipeline in straight-line code -- no predicate per
+    // group, one fresh group, one reduction outside the MFMAs' shadow, no fragment request behind the last group.  The bound
+    // is built once from the key as it stands (a stale bound is only looser: the key never increases) and the four head
+    // values are tested against it with one ballot.  A tile in which some group fails goes through the rolled loop behind:
+    // both accumulator sets are free by then, the failed groups are recomputed from the slots they sit in -- in front of the
+    // barrier that frees those -- and head_finish rebuilds the bound from the key a finish_group may have refreshed.
+    auto head_tile_lean = [&](int buf0, int buf1, int j0) __attribute__((always_inline)) {
+        if constexpr (HEAD > 0 && SPAN == 2) {
+            static_assert(RSUB == 2, "two slots of two groups");
+            float bound_f = pre_f;
+            const uint32_t best_bits = (uint32_t)(gk >> 32);
+            if (best_bits != 0xffffffffu) {
+                const float bb = hm::bitsf(best_bits + hm_tie_slack(best_bits)) + 2.0f * delta;
+                if (bb < bound_f) bound_f = bb;
+            }
+            const char* b0 = head_at(buf0, 0);
+            const char* b1 = head_at(buf1, 0);
+            float e0 = 0.0f, e1 = 0.0f, e2 = 0.0f;
+            head_group(std::integral_constant<int, 0>{}, std::false_type{}, std::true_type{}, b0, b0 + 32 * RB16, true, e0);
+            head_group(std::integral_constant<int, 1>{}, std::true_type{}, std::true_type{}, b0 + 32 * RB16, b1, false, e0);
+            head_group(std::integral_constant<int, 0>{}, std::true_type{}, std::true_type{}, b1, b1 + 32 * RB16, false, e1);
+            head_group(std::integral_constant<int, 1>{}, std::true_type{}, std::false_type{}, b1 + 32 * RB16, b1, false, e2);
+            const float e3 = reduce_group(std::integral_constant<int, 1>{});
+            hg_tot += 2 * RSUB;
+            if (__ballot(__builtin_fminf(__builtin_fminf(e0, e1), __builtin_fminf(e2, e3)) < bound_f) != 0ull) {
+#pragma unroll 1
+                for (int g = 0; g < 2 * RSUB; ++g) {
+                    const float eg = g == 0 ? e0 : (g == 1 ? e1 : (g == 2 ? e2 : e3));
+                    hc_tot += head_finish(std::integral_constant<int, 0>{}, eg, g < RSUB ? buf0 : buf1, g % RSUB, j0 + 32 * g) ? 1 : 0;
+                }
+            }
+        }
+    };
+
     // ---- work distribution: block b owns item b of the host's list (hm_scan_plan.h); with the item queue (p.dyn) the grid
     // is the resident set and every block goes on drawing items of the same list, in order, from the queue word p.q_ctr ----
     volatile uint32_t* const qslot = reinterpret_cast<volatile uint32_t*>(smem + G::queue_off(MODE));      // the drawn counter value, for all waves
@@ -663,7 +774,7 @@ __global__ __launch_bounds__(64 * WPB, 2) void hm_scan_kernel(const ScanArgs p)
         // the tiles the run has, no repeats (the loop below requests none either); everything lands before the loop is
         // entered -- the wait hipcc can see (below) would drain the prologue's tiles anyway, once per item
 #pragma unroll
-        for (int q = 0; q < DIST; ++q)
+        for (int q = 0; q < NBUF - SPAN; ++q)              // (ScanRun::prologue: DIST slots ahead of span 1, one fewer of span 2)
             if (q < ntile) dma_tile(tile_at(q), q);
         __builtin_amdgcn_s_waitcnt(0x0F70);
     } else {
@@ -684,6 +795,56 @@ __global__ __launch_bounds__(64 * WPB, 2) void hm_scan_kernel(const ScanArgs p)
     int buf = 0;                     // ring slot of tile t
     int gk_due = 0;                  // RING > 0: the tile behind whose wait the key load in flight is complete
 
+    if constexpr (SPAN == 2) {
+        // the span-2 walk (ScanRun of hm_scan_geom.h): two ring slots per barrier.  Tile k computes the slots 2k and 2k + 1
+        // of the run (an odd run ends on a tile of one), which sit in the ring slots buf and buf + 1; the slots it requests
+        // go to the two ring slots behind those of tile k + 1, the ones tile k - 1 computed.
+        static_assert(HEAD > 0 && RING > 0 && MODE == HM_MODE_ARGMIN, "the span-2 walk is the head kernels'");
+        const ScanRun run{ntile, NBUF, SPAN};
+        const int ntk = run.tiles();
+        const int j_right = rb * BLOCK_ROWS + BLOCK_ROWS;      // columns from here on lie right of every row of the block
+        auto ring_add = [&](int b, int q) { b += q; return b >= NBUF ? b - NBUF : b; };
+#pragma unroll 1
+        for (int k = 0; k < ntk; ++k) {
+            const int nslot = run.count(k);
+            const int j0 = (ct0 + 2 * k) * COLS;
+            const int buf1 = ring_add(buf, 1);
+            const bool last = (k == ntk - 1);
+            // the running key every 8th tile (128 columns: a plan tile), into its fixed registers (see the span-1 walk below);
+            // issued ahead of the tile's requests, so the tile's own wait covers it (ScanRun)
+            const bool poll = (k & 7) == 0;
+            if (poll) asm volatile("global_load_dwordx2 v[252:253], %0, off sc1" : : "v"(&p.ctr64[1]) : "memory", "v252", "v253");
+            if (dyn && last && threadIdx.x == 0)
+                asm volatile("global_atomic_add_x2 v[254:255], %0, %1, off sc0" : : "v"(p.q_ctr), "v"(1ull) : "memory", "v254", "v255");
+            {
+                const int rq = run.req_first(k), nrq = run.req_count(k);
+                const int bq = ring_add(buf, NBUF - SPAN);
+                if (nrq > 0) dma_tile(ct0 + rq, bq);
+                if (nrq > 1) dma_tile(ct0 + rq + 1, ring_add(bq, 1));
+            }
+            if (nslot == 2 && wave_active && j0 >= j_right) {
+                head_tile_lean(buf, buf1, j0);
+            } else {
+                // a tile on the diagonal, a wave without rows, a run's odd end: slot by slot, every group with its predicate
+#pragma unroll 1
+                for (int sl = 0; sl < nslot; ++sl) head_walk(sl ? buf1 : buf, j0 + sl * COLS);
+            }
+            ring_wait(run.outstanding(k));
+            if (poll) {
+                uint32_t klo, khi;
+                asm volatile("v_mov_b32 %0, v252\n\tv_mov_b32 %1, v253" : "=v"(klo), "=v"(khi) : : "memory", "v252", "v253");
+                gk_raw = ((unsigned long long)khi << 32) | klo;
+                if (gk_raw < gk) gk = gk_raw;                   // the key only ever decreases
+            }
+            if (dyn && last && threadIdx.x == 0) {
+                uint32_t qlo, qhi;
+                asm volatile("v_mov_b32 %0, v254\n\tv_mov_b32 %1, v255" : "=v"(qlo), "=v"(qhi) : : "memory", "v254", "v255");
+                qslot[0] = qlo; qslot[1] = qhi;
+            }
+            __syncthreads();                                 // every wave's pieces have landed; all reads of the tile's slots done
+            buf = ring_add(buf, SPAN);
+        }
+    } else
     for (int t = 0; t < ntile; ++t) {
         const int ct = tile_at(t);
         const int ct_next = (t + DIST < ntile) ? tile_at(t + DIST) : ct;      // (a repeat of this tile lands in the free slot)
@@ -724,44 +885,7 @@ __global__ __launch_bounds__(64 * WPB, 2) void hm_scan_kernel(const ScanArgs p)
         }
 
         if constexpr (HEAD > 0) {           // a head kernel walks every tile this way
-            // head walk: the groups of the tile alternate between the accumulator sets; group g's head k-steps carry the
-            // reduction of group g - 1's head values, whose test follows.  Nothing is pending across the tile's barrier (the
-            // recomputation of a failed group reads its columns from this ring slot): the last group is reduced on its own.
-            bool hp = false;
-            int hg = 0, hc = 0;          // groups of this tile that ran / that had to be recomputed
-#pragma unroll 1
-            for (int sp = 0; sp < RSUB / 2; ++sp) {
-                {
-                    const int sub = 2 * sp;
-                    const int j0s = j0 + sub * 32;
-                    const bool do_c = wave_active && (j0s + 31 > i0w);
-                    float ext_u = 0.0f;
-                    if (do_c && hp) {
-                        head_group(std::integral_constant<int, 0>{}, std::true_type{}, buf, sub, false, ext_u);
-                    } else {
-                        if (do_c) head_group(std::integral_constant<int, 0>{}, std::false_type{}, buf, sub, true, ext_u);
-                        if (hp) ext_u = reduce_group(std::integral_constant<int, 1>{});
-                    }
-                    if (hp) { ++hg; hc += head_finish(std::integral_constant<int, 1>{}, ext_u, buf, sub - 1, j0s - 32) ? 1 : 0; }
-                    hp = do_c;
-                }
-                {
-                    const int sub = 2 * sp + 1;
-                    const int j0s = j0 + sub * 32;
-                    const bool do_c = wave_active && (j0s + 31 > i0w);
-                    float ext_u = 0.0f;
-                    if (do_c && hp) {
-                        head_group(std::integral_constant<int, 1>{}, std::true_type{}, buf, sub, false, ext_u);
-                    } else {
-                        if (do_c) head_group(std::integral_constant<int, 1>{}, std::false_type{}, buf, sub, true, ext_u);
-                        if (hp) ext_u = reduce_group(std::integral_constant<int, 0>{});
-                    }
-                    if (hp) { ++hg; hc += head_finish(std::integral_constant<int, 0>{}, ext_u, buf, sub - 1, j0s - 32) ? 1 : 0; }
-                    hp = do_c;
-                }
-            }
-            if (hp) { ++hg; hc += head_finish(std::integral_constant<int, 1>{}, reduce_group(std::integral_constant<int, 1>{}), buf, RSUB - 1, j0 + (RSUB - 1) * 32) ? 1 : 0; }
-            hg_tot += hg; hc_tot += hc;
+            head_walk(buf, j0);
         } else if constexpr (!PIPE) {
             // one accumulator set: MFMAs, then the bound test of the same group (the other resident block of the CU
             // fills the matrix pipe meanwhile); the first fragment of the next group is still requested early
@@ -832,25 +956,6 @@ __global__ __launch_bounds__(64 * WPB, 2) void hm_scan_kernel(const ScanArgs p)
 
         // tile t+1 has landed (this wave's pieces) -- and so has the key load, if one was issued
         if constexpr (RING > 0) {
-            // the counted wait that leaves the pieces of at most `tiles` (wave-uniform; DIST - 1 at most count) of this wave's
-            // tiles outstanding; a key load or a queue draw among the outstanding only makes the count stricter
-            auto ring_wait = [&](int tiles) __attribute__((always_inline)) {
-                auto wait_p = [&](auto p_c) __attribute__((always_inline)) {
-                    constexpr int P = decltype(p_c)::value;
-                    static_assert((DIST - 1) * P <= 60, "the counted wait must fit vmcnt");
-                    if (tiles >= 3 && DIST > 3) asm volatile("s_waitcnt vmcnt(%0)" : : "n"(3 * P) : "memory");
-                    else if (tiles >= 2 && DIST > 2) asm volatile("s_waitcnt vmcnt(%0)" : : "n"(2 * P) : "memory");
-                    else if (tiles >= 1 && DIST > 1) asm volatile("s_waitcnt vmcnt(%0)" : : "n"(P) : "memory");
-                    else asm volatile("s_waitcnt vmcnt(0)" : : : "memory");
-                };
-                static_assert(DIST <= 4, "ring_wait writes out the depths");
-                if constexpr (PREM != 0) {
-                    if (wave < PREM) wait_p(std::integral_constant<int, PQ + 1>{});
-                    else wait_p(std::integral_constant<int, PQ>{});
-                } else {
-                    wait_p(std::integral_constant<int, G::EXACT ? PQ : PPW>{});
-                }
-            };
             // tiles t + 2 .. of the run may stay in flight, DIST - 1 of them at most; behind the last tile nothing does
             ring_wait(ntile - 2 - t);
             // the key load is complete once the wait has passed the tile requested right behind it (tile t_issue + DIST: loads
@@ -931,13 +1036,13 @@ __global__ __launch_bounds__(64 * WPB, 2) void hm_scan_kernel(const ScanArgs p)
 // ------------------------------------------------------------------------------------------------
 // launch
 // ------------------------------------------------------------------------------------------------
-template <int NG, int SIGN, int MODE, int BF, int TM, int WPB, int SUB, bool WK = false, int HEAD = 0, int RING = 0>
+template <int NG, int SIGN, int MODE, int BF, int TM, int WPB, int SUB, bool WK = false, int HEAD = 0, int RING = 0, int SPAN = 1>
 static hipError_t hm_launch_scan_t(hm_engine* e, const ScanArgs& a, dim3 grid, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1)
 {
-    using G = ScanGeom<NG, BF, TM, WPB, SUB, RING>;
+    using G = ScanGeom<NG, BF, TM, WPB, SUB, RING, SPAN>;
     const size_t lds = G::lds_bytes(MODE);
     static_assert(RING == 0 || G::lds_bytes(MODE) <= HM_LDS_PER_BLOCK, "a deeper ring keeps two blocks per CU");
-    const void* fn = reinterpret_cast<const void*>(&hm_scan_kernel<NG, SIGN, MODE, BF, TM, WPB, SUB, WK, HEAD, RING>);
+    const void* fn = reinterpret_cast<const void*>(&hm_scan_kernel<NG, SIGN, MODE, BF, TM, WPB, SUB, WK, HEAD, RING, SPAN>);
     if (lds > 48 * 1024 && e->attr_done.find(fn) == e->attr_done.end()) {     // per engine (= per device), not process-wide
         hipError_t st = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (st != hipSuccess) return st;
@@ -966,8 +1071,8 @@ static hipError_t hm_launch_scan_t(hm_engine* e, const ScanArgs& a, dim3 grid, h
             b.q_ctr = e->d_queue + 16 * ((b.ctr64 == e->d_ctr64) ? 0 : 1);      // one word per counter set (the pipelined loop alternates them)
         }
     }
-    if (ev0 != nullptr || ev1 != nullptr) hipExtLaunchKernelGGL((hm_scan_kernel<NG, SIGN, MODE, BF, TM, WPB, SUB, WK, HEAD, RING>), grid, dim3(G::NTHREADS), lds, s, ev0, ev1, 0, b);
-    else hipLaunchKernelGGL((hm_scan_kernel<NG, SIGN, MODE, BF, TM, WPB, SUB, WK, HEAD, RING>), grid, dim3(G::NTHREADS), lds, s, b);
+    if (ev0 != nullptr || ev1 != nullptr) hipExtLaunchKernelGGL((hm_scan_kernel<NG, SIGN, MODE, BF, TM, WPB, SUB, WK, HEAD, RING, SPAN>), grid, dim3(G::NTHREADS), lds, s, ev0, ev1, 0, b);
+    else hipLaunchKernelGGL((hm_scan_kernel<NG, SIGN, MODE, BF, TM, WPB, SUB, WK, HEAD, RING, SPAN>), grid, dim3(G::NTHREADS), lds, s, b);
     return hipGetLastError();
 }
 
@@ -983,13 +1088,19 @@ static hipError_t hm_launch_scan_ng(hm_engine* e, int sign, int mode, const Scan
             constexpr int HD = (BF != 0 && TM <= HM_SCAN_PIPE_MAX_TM) ? hm_head_steps(NG) : 0;
             if constexpr (HD > 0) {
                 if (hm_head_live(e)) {
-                    // the head kernels' ring (kScanRings; knob `head_ring`): the one place that gives a kernel another ring than 0
-#define HM_HEAD_RING_CASE(R)                                                                                               \
-    case R:                                                                                                                \
-        if (a.key_wide) return hm_launch_scan_t<NG, 1, HM_MODE_ARGMIN, BF, TM, WPB, SUB, true, HD, R>(e, a, grid, s, ev0, ev1); \
-        return hm_launch_scan_t<NG, 1, HM_MODE_ARGMIN, BF, TM, WPB, SUB, false, HD, R>(e, a, grid, s, ev0, ev1);
-                    static_assert(HM_SCAN_RINGS == 3, "one case per ring");
-                    switch (e->head_ring) { HM_HEAD_RING_CASE(0) HM_HEAD_RING_CASE(1) HM_HEAD_RING_CASE(2) }
+                    // the head kernels' ring and span (kScanRings, ScanRun; knobs `head_ring`, `head_span`): the one place that gives
+                    // a kernel another ring than 0 or another span than 1.  A span the width's ring has no slots for is the
+                    // geometry's to replace (ScanGeom::SPAN): that launch takes the ring's span-1 kernel
+#define HM_HEAD_RING_CASE(R, S)                                                                                            \
+    case 4 * S + R: {                                                                                                      \
+        constexpr int SP = ScanGeom<NG, BF, TM, WPB, SUB, R, S>::SPAN;                                                     \
+        if (a.key_wide) return hm_launch_scan_t<NG, 1, HM_MODE_ARGMIN, BF, TM, WPB, SUB, true, HD, R, SP>(e, a, grid, s, ev0, ev1); \
+        return hm_launch_scan_t<NG, 1, HM_MODE_ARGMIN, BF, TM, WPB, SUB, false, HD, R, SP>(e, a, grid, s, ev0, ev1);       \
+    }
+                    static_assert(HM_SCAN_RINGS == 3, "one case per ring and span");
+                    switch (4 * (e->head_ring == 0 ? 1 : e->head_span) + e->head_ring) {      // (ring 0 ignores the span)
+                        HM_HEAD_RING_CASE(0, 1) HM_HEAD_RING_CASE(1, 1) HM_HEAD_RING_CASE(2, 1) HM_HEAD_RING_CASE(1, 2) HM_HEAD_RING_CASE(2, 2)
+                    }
 #undef HM_HEAD_RING_CASE
                     return hipErrorInvalidValue;
                 }

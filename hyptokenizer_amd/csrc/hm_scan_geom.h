@@ -79,7 +79,37 @@ constexpr ScanRing kScanRings[HM_SCAN_RINGS] = {{0, 0, 0}, {2, 3, 0}, {2, 4, 1}}
 // the head kernels' ring (knob `head_ring`).  Measured at 50 000 rows, interleaved in one process (profiles/scan_head_ring_ab.json):
 // ring 1 takes 2.5 - 4 % off the scan launch of ring 0; ring 2 -- a third more in flight and no padding traffic -- none
 #define HM_SCAN_HEAD_RING_DEFAULT 1
+// slots the head kernels compute per barrier (knob `head_span`; ring 0 has none to choose).  Measured at 50 000 and 100 000
+// rows, interleaved in one process (profiles/scan_head_span_ab.json): span 2 takes 16 % and 12 % off the scan launch of
+// span 1 on ring 1, and ring 2 x span 2 is within half a percent of ring 1 x span 2 at either size
+#define HM_SCAN_HEAD_SPAN_DEFAULT 2
 #define HM_LDS_PER_BLOCK (80 * 1024)  // half of a CU's 160 KiB: what a block may use with two blocks resident
+
+// ---- the walk of a run over a ring: `span` consecutive slots are computed between two barriers (a compute tile); span 1
+// is the walk of every kernel but the span-2 head kernels (knob `head_span`).  A run of `ntile` slots over `nbuf` ring
+// slots, slot s in ring slot s % nbuf:
+//   prologue    requests slots 0 .. nbuf - span - 1 (those the run has) and waits for all of them
+//   tile k      computes slots k * span .. (an odd run ends on a tile of fewer); at its start it requests the slots
+//               nbuf + (k - 1) * span .. nbuf + k * span - 1 -- into the ring slots tile k - 1 computed, which every wave left
+//               at the barrier in between --; its wait, in front of the barrier that ends it, lets the slots of tile k + 1 land
+// Tile 0 computes slots the prologue requested and tile k's requests must not touch the slots it computes: nbuf >= 2 * span.
+// What the wait of tile k leaves outstanding was requested in tile k itself, behind the tile's key load and queue draw: a
+// counted wait that names those slots' pieces has passed both (vector-memory loads return in order).
+// The kernel (hm_scan.hip) and tests/scan_span_driver.cpp run this code.
+struct ScanRun {
+    int ntile, nbuf, span;
+    HM_HOST_DEVICE_INLINE constexpr int clamp(int s) const { return s < 0 ? 0 : (s > ntile ? ntile : s); }
+    HM_HOST_DEVICE_INLINE constexpr int tiles() const { return (ntile + span - 1) / span; }
+    HM_HOST_DEVICE_INLINE constexpr int prologue() const { return clamp(nbuf - span); }                  // slots requested before tile 0
+    HM_HOST_DEVICE_INLINE constexpr int first(int k) const { return k * span; }                          // tile k computes [first, first + count)
+    HM_HOST_DEVICE_INLINE constexpr int count(int k) const { return clamp((k + 1) * span) - clamp(k * span); }
+    HM_HOST_DEVICE_INLINE constexpr int req_first(int k) const { return clamp(nbuf + (k - 1) * span); }  // tile k requests [req_first, req_first + req_count)
+    HM_HOST_DEVICE_INLINE constexpr int req_count(int k) const { return clamp(nbuf + k * span) - req_first(k); }
+    // slots still in flight behind the wait of tile k: everything requested so far but the slots of tile k + 1
+    HM_HOST_DEVICE_INLINE constexpr int outstanding(int k) const { return clamp(nbuf + k * span) - clamp((k + 2) * span); }
+    // the most that can be: what the counted waits are written out for
+    HM_HOST_DEVICE_INLINE static constexpr int outstanding_max(int nbuf, int span) { return nbuf - 2 * span; }
+};
 
 // ---- what follows from a kernel's template arguments.  LDS map of a block (dynamic shared memory, from offset 0):
 //   ring    NBUF slots of TILE_LDS bytes: the streamed partner tiles
@@ -87,7 +117,7 @@ constexpr ScanRing kScanRings[HM_SCAN_RINGS] = {{0, 0, 0}, {2, 3, 0}, {2, 4, 1}}
 //           here and is never used.  HIST mode keeps its HM_HIST_BINS bins at the same offset (they are only read by that
 //           request) and the slack's bytes behind them
 //   queue   16 bytes: the item queue's broadcast word
-template <int NG, int BF, int TM, int WPB, int SUB, int RING = 0>
+template <int NG, int BF, int TM, int WPB, int SUB, int RING = 0, int SPAN_ASK = 1>
 struct ScanGeom {
     static_assert(RING >= 0 && RING < HM_SCAN_RINGS && (RING == 0 || BF != 0), "rings other than 0: bf16 form");
     static constexpr int RSUB = kScanRings[RING].sub ? kScanRings[RING].sub : SUB;   // 32-column groups per ring slot
@@ -115,11 +145,17 @@ struct ScanGeom {
     static constexpr int DIST = RING == 0 ? (BF ? HM_DIST_BF16 : 1)
                                           : (kScanRings[RING].dist + 1 <= SLOTS_MAX ? kScanRings[RING].dist : (SLOTS_MAX > 2 ? SLOTS_MAX - 1 : 1));
     static constexpr int NBUF = DIST + 1;                   // ring slots
+    // slots computed per barrier (ScanRun): what was asked for where the ring has the slots for it (16 chunks keep 3 padded
+    // slots: span 1), and 1 on ring 0
+    static_assert(SPAN_ASK == 1 || SPAN_ASK == 2, "the walks that are written out");
+    static constexpr int SPAN = (RING != 0 && NBUF >= 2 * SPAN_ASK) ? SPAN_ASK : 1;
+    static_assert(SPAN == 1 || NBUF >= 2 * SPAN, "a compute tile's slots and the next one's are in the ring together");
     static constexpr int WAVE_ROWS = 32 * TM;
     static constexpr int BLOCK_ROWS = WPB * WAVE_ROWS;
     static constexpr int NTHREADS = 64 * WPB;
     static_assert(TILE_BYTES % 1024 == 0, "tiles are moved in 1 KiB pieces");
     static_assert(DIST * PPW <= 60, "the counted wait must fit vmcnt");
+    static_assert(SPAN == 1 || ScanRun::outstanding_max(NBUF, SPAN) <= DIST - SPAN, "a span's waits leave less in flight than span 1's");
 
     static constexpr int RING_BYTES = NBUF * TILE_LDS;
     static constexpr int SLACK_BYTES = 32 * ROW_BYTES;
