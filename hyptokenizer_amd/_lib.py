@@ -55,7 +55,8 @@ EXPORTED_SYMBOLS = (
     "hm_graph_create", "hm_graph_destroy", "hm_graph_set_csr", "hm_graph_components", "hm_graph_pair_lengths",
     "hm_graph_distance_rows", "hm_graph_last_stats", "hm_tokstats",
     "hm_rsgd_step", "hm_radam_step",
-    "hm_edge_loss_fwd", "hm_edge_loss_bwd", "hm_debug_edge_loss_form", "hm_negsample_create", "hm_negsample_destroy", "hm_negsample_check_csr",
+    "hm_edge_loss_fwd", "hm_edge_loss_bwd", "hm_debug_edge_loss_form", "hm_cone_loss_fwd", "hm_cone_loss_bwd", "hm_debug_cone_loss_form",
+    "hm_negsample_create", "hm_negsample_destroy", "hm_negsample_check_csr",
     "hm_negsample_set_csr", "hm_negsample_sample",
     "hm_centroid_fwd", "hm_centroid_bwd", "hm_debug_centroid_form",
     "hm_recon_slots", "hm_recon_counts", "hm_debug_recon_layout",
@@ -203,6 +204,9 @@ def load() -> C.CDLL:
     L.hm_edge_loss_fwd.argtypes = [vp, i64, i64, C.c_int, vp, i64, i64, f32, vp, vp, vp]
     L.hm_edge_loss_bwd.argtypes = [vp, i64, i64, C.c_int, vp, i64, i64, f32, vp, vp, vp, vp, vp]
     L.hm_debug_edge_loss_form.argtypes = [C.c_int]
+    L.hm_cone_loss_fwd.argtypes = [vp, i64, i64, C.c_int, vp, i64, i64, f32, f32, C.c_int, vp, vp, vp]
+    L.hm_cone_loss_bwd.argtypes = [vp, i64, i64, C.c_int, vp, i64, i64, f32, f32, C.c_int, vp, vp, vp, vp, vp]
+    L.hm_debug_cone_loss_form.argtypes = [C.c_int]
     L.hm_centroid_fwd.argtypes = [vp, i64, i64, C.c_int, vp, i64, vp, vp, vp, i64, vp, vp, vp]
     L.hm_centroid_bwd.argtypes = [vp, i64, i64, C.c_int, vp, i64, vp, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp]
     L.hm_debug_centroid_form.argtypes = [C.c_int]

@@ -17,7 +17,7 @@
 //   form 1  one WAVE per sample: its S groups take the partners k = g, g + S, g + 2 S, ... and combine d_min, the sum of
 //           exponentials and the anchor's gradient by butterflies across the wave -- S times the waves, P / S the walk.
 // Below, "position" i of group g is partner k = g + S i (form 0: S = 1, g = 0).
-//   forward   pass 1: u_k by the whole group (el_canon_sum: hm_halfwave_sum's chains laid over the group's slots), parked in
+//   forward   pass 1: u_k by the whole group (rg_canon_sum: hm_halfwave_sum's chains laid over the group's slots), parked in
 //             lane k % G, which evaluates d_k once and stores u_k to the weights w [B, P];
 //             pass 2: every lane re-reads the u_k IT stored, sums exp(-(d_k - d_min)), one butterfly;
 //             pass 3: the same lanes turn their u_k into a_k in place.
@@ -44,107 +44,11 @@ struct ElArgs {
     float sqrt_c;
 };
 
-__device__ __forceinline__ float el_pick(const float (&p)[4], int j) { return j == 0 ? p[0] : j == 1 ? p[1] : j == 2 ? p[2] : p[3]; }
-
-// Sum of the row's d products pr (element e in slot e >> lsh of lane e & (G - 1); slots past d hold 0) in the order of
-// hm::torch_order_sum, bit for bit, on every lane of the group.  ATen's 32 chains: chain t takes elements t, t + 32, ... below
-// 32 ilp; a group of 32 lanes holds chain t in lane t (slots 0 .. ilp - 1), a group of 16 holds chains t and t + 16 in lane t
-// (even and odd slots).  Then hm_halfwave_sum's combine: leftover vectors of 8 into chains 0..7, chains l, l + 8, l + 16,
-// l + 24 added in that order, the scalar tail summed from zero, the eight sums in order.  Every branch is uniform.
-__device__ __forceinline__ float el_canon_sum(const RgMap& q, int d, const float (&pr)[4])
-{
-    const int G = 1 << q.lsh, t = q.sub;
-    if (d < 8) {                                              // scalar form: element e is slot 0 of lane e (G = 16)
-        float ps[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-        const int full = (d >> 2) * 4;
-#pragma unroll
-        for (int e = 0; e < 7; ++e) {
-            const float v = __shfl(pr[0], e, 16);
-            if (e < full) ps[e & 3] = ps[e & 3] + v;
-            else if (e < d) ps[0] = ps[0] + v;
-        }
-        ps[0] = ps[0] + ps[1];
-        ps[0] = ps[0] + ps[2];
-        ps[0] = ps[0] + ps[3];
-        return ps[0];
-    }
-    const int vec = d >> 3, ilp = vec >> 2, nleft = vec - ilp * 4, ntail = d - vec * 8;
-    float pa = 0.0f, pb = 0.0f;
-    float c1, c2, c3;
-    if (q.lsh == 5) {
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-            if (j < ilp) pa = pa + pr[j];
-    } else {
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-            if (i < ilp) { pa = pa + pr[2 * i]; pb = pb + pr[2 * i + 1]; }
-    }
-#pragma unroll
-    for (int v = 0; v < 3; ++v) {
-        if (v < nleft) {
-            const int e0 = 32 * ilp + 8 * v;                  // first element of the leftover vector: 8 elements of one slot
-            const float got = __shfl(el_pick(pr, e0 >> q.lsh), (e0 & (G - 1)) + (t & 7), G);
-            if (t < 8) pa = pa + got;
-        }
-    }
-    if (q.lsh == 5) {
-        c1 = __shfl(pa, (t & 7) + 8, 32);
-        c2 = __shfl(pa, (t & 7) + 16, 32);
-        c3 = __shfl(pa, (t & 7) + 24, 32);
-    } else {
-        c1 = __shfl(pa, (t & 7) + 8, 16);
-        c2 = __shfl(pb, (t & 7), 16);
-        c3 = __shfl(pb, (t & 7) + 8, 16);
-    }
-    const float r = ((pa + c1) + c2) + c3;                    // meaningful on lanes t < 8
-    float acc = 0.0f;
-#pragma unroll
-    for (int v = 0; v < 7; ++v) {
-        if (v < ntail) {
-            const int e = vec * 8 + v;
-            acc = acc + __shfl(el_pick(pr, e >> q.lsh), e & (G - 1), G);
-        }
-    }
-#pragma unroll
-    for (int l = 0; l < 8; ++l) acc = acc + __shfl(r, l, G);
-    return acc;
-}
-
-// butterflies over the lanes that share a sample: `width` = the group (form 0) or the wave (form 1)
-__device__ __forceinline__ float el_min(int width, float a)
-{
-    for (int off = width >> 1; off > 0; off >>= 1) a = fminf(a, __shfl_xor(a, off, 64));
-    return a;
-}
-__device__ __forceinline__ float el_sum(int width, float a)
-{
-    for (int off = width >> 1; off > 0; off >>= 1) a = a + __shfl_xor(a, off, 64);
-    return a;
-}
-
-// the sample of this group: its anchor and whether it is served
-struct ElSample {
-    const int64_t* ix;
-    int64_t iu;
-    bool ok;
-};
-
-__device__ __forceinline__ ElSample el_sample(const ElArgs& a, const RgMap& q)
-{
-    ElSample s;
-    s.ix = a.index + q.row * (int64_t)(2 + a.K);
-    s.iu = q.live ? s.ix[0] : -1;
-    const int64_t iv = q.live ? s.ix[1] : -1;
-    s.ok = q.live && rg_in(s.iu, a.V) && rg_in(iv, a.V);
-    return s;
-}
-
 __global__ __launch_bounds__(EL_THREADS) void hm_el_fwd_kernel(const ElArgs a)
 {
     int gid, S;
     const RgMap q = rg_split_map(a.lsh, a.split, a.B, gid, S);
-    const ElSample s = el_sample(a, q);
+    const RgSample s = rg_sample(a.index, a.K, a.V, q);
     const int G = 1 << a.lsh, d = a.d, P = 1 + a.K;
     const int Pp = (P + S - 1) / S, width = G * S;               // positions per group; lanes that share the sample
     RgMap qa = q;
@@ -185,7 +89,7 @@ __global__ __launch_bounds__(EL_THREADS) void hm_el_fwd_kernel(const ElArgs a)
                 float pr[4];
 #pragma unroll
                 for (int j = 0; j < 4; ++j) pr[j] = xs[j] * ys[r][j];
-                const float S = el_canon_sum(q, d, pr);
+                const float S = rg_canon_sum(q, d, pr);
                 const float t0 = x0 * y0[r];
                 const float u = (idx[r] == s.iu) ? 1.0f : t0 - S;
                 if (q.sub == kk + r) { myu = u; mylive = lv[r]; }
@@ -195,7 +99,7 @@ __global__ __launch_bounds__(EL_THREADS) void hm_el_fwd_kernel(const ElArgs a)
         const float dk = mylive ? hm::dist_from_u(myu, a.sqrt_c) : INFINITY;
         if (q.live && k < P) wr[k] = mylive ? myu : 1.0f;
         if (c0 == 0) d0 = __shfl(dk, 0, width);                  // partner 0: position 0 of group 0
-        dmin = fminf(dmin, el_min(width, dk));
+        dmin = fminf(dmin, rg_wave_min(width, dk));
     }
 
     // pass 2: the shifted sum, every lane over the slots it stored
@@ -204,7 +108,7 @@ __global__ __launch_bounds__(EL_THREADS) void hm_el_fwd_kernel(const ElArgs a)
         const int k = gid + S * (c0 + q.sub);
         if (s.ok && k < P && rg_in(s.ix[1 + k], a.V)) sum = sum + expf(dmin - hm::dist_from_u(wr[k], a.sqrt_c));
     }
-    sum = el_sum(width, sum);
+    sum = rg_wave_sum(width, sum);
     const float lse = logf(sum) - dmin;
     if (q.live && q.sub == 0 && gid == 0) a.loss[q.row] = s.ok ? d0 + lse : 0.0f;
 
@@ -228,7 +132,7 @@ __global__ __launch_bounds__(EL_THREADS) void hm_el_bwd_kernel(const ElArgs a)
 {
     int gid, S;
     const RgMap q = rg_split_map(a.lsh, a.split, a.B, gid, S);
-    const ElSample s = el_sample(a, q);
+    const RgSample s = rg_sample(a.index, a.K, a.V, q);
     const int d = a.d, d1 = a.d + 1, P = 1 + a.K;
     const int Pp = (P + S - 1) / S;
     RgMap qa = q;

@@ -1,5 +1,5 @@
 // hm_rowgroup.h -- "a group of lanes owns a row": the layout of the row-wise kernels that keep a whole row in registers
-// (hm_poincare.hip, hm_riemann.hip, hm_edgeloss.hip, hm_pool.hip).
+// (hm_poincare.hip, hm_riemann.hip, hm_edgeloss.hip, hm_cones.hip, hm_pool.hip).
 //
 // A row of width d <= HM_RG_MAX_D is owned by a group of 16 (d <= 64) or 32 lanes of one wave; a wave therefore carries 4
 // or 2 rows and a load instruction of the wave always covers whole rows.  A lane holds four slots of its row:
@@ -17,7 +17,9 @@
 // dereferenced, reads as (dead_t, 0, .., 0) and takes part in butterflies only.  rg_gather is the flight of such rows; two
 // kernels (edge-loss forward, pooling backward) keep theirs written out for speed.  A kernel that walks gathered rows
 // is launched in one of two forms (rg_split_map): a group per row, or a wave per row whose S groups share the walk and
-// fold their partial sums across the wave (rg_fold_groups).
+// fold their partial sums across the wave (rg_fold_groups).  The two losses on an index [rows, 2 + K] (hm_edgeloss.hip,
+// hm_cones.hip) share rg_sample, the anchor / positive test of an index row, and rg_canon_sum, the sum of a row's products
+// in ATen's order on the group's slots, with the butterflies over a sample's lanes (rg_wave_min, rg_wave_sum).
 #pragma once
 #include "hm_common.h"
 
@@ -162,6 +164,103 @@ __device__ __forceinline__ void rg_fold_groups(int lsh, int S, RgRow& v)
 #pragma unroll
         for (int j = 0; j < 4; ++j) v.s[j] = v.s[j] + __shfl_xor(v.s[j], off, 64);
     }
+}
+
+// the sample of this group in an index [rows, 2 + K] (anchor, positive, K negatives): its anchor and whether it is served --
+// a sample whose anchor or positive lies outside [0, V) is not
+struct RgSample {
+    const int64_t* ix;
+    int64_t iu;
+    bool ok;
+};
+
+__device__ __forceinline__ RgSample rg_sample(const int64_t* __restrict__ index, int K, int64_t V, const RgMap& q)
+{
+    RgSample s;
+    s.ix = index + q.row * (int64_t)(2 + K);
+    s.iu = q.live ? s.ix[0] : -1;
+    const int64_t iv = q.live ? s.ix[1] : -1;
+    s.ok = q.live && rg_in(s.iu, V) && rg_in(iv, V);
+    return s;
+}
+
+__device__ __forceinline__ float rg_pick(const float (&p)[4], int j) { return j == 0 ? p[0] : j == 1 ? p[1] : j == 2 ? p[2] : p[3]; }
+
+// Sum of the row's d products pr (element e in slot e >> lsh of lane e & (G - 1); slots past d hold 0) in the order of
+// hm::torch_order_sum, bit for bit, on every lane of the group.  ATen's 32 chains: chain t takes elements t, t + 32, ... below
+// 32 ilp; a group of 32 lanes holds chain t in lane t (slots 0 .. ilp - 1), a group of 16 holds chains t and t + 16 in lane t
+// (even and odd slots).  Then hm_halfwave_sum's combine: leftover vectors of 8 into chains 0..7, chains l, l + 8, l + 16,
+// l + 24 added in that order, the scalar tail summed from zero, the eight sums in order.  Every branch is uniform.
+__device__ __forceinline__ float rg_canon_sum(const RgMap& q, int d, const float (&pr)[4])
+{
+    const int G = 1 << q.lsh, t = q.sub;
+    if (d < 8) {                                              // scalar form: element e is slot 0 of lane e (G = 16)
+        float ps[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+        const int full = (d >> 2) * 4;
+#pragma unroll
+        for (int e = 0; e < 7; ++e) {
+            const float v = __shfl(pr[0], e, 16);
+            if (e < full) ps[e & 3] = ps[e & 3] + v;
+            else if (e < d) ps[0] = ps[0] + v;
+        }
+        ps[0] = ps[0] + ps[1];
+        ps[0] = ps[0] + ps[2];
+        ps[0] = ps[0] + ps[3];
+        return ps[0];
+    }
+    const int vec = d >> 3, ilp = vec >> 2, nleft = vec - ilp * 4, ntail = d - vec * 8;
+    float pa = 0.0f, pb = 0.0f;
+    float c1, c2, c3;
+    if (q.lsh == 5) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+            if (j < ilp) pa = pa + pr[j];
+    } else {
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+            if (i < ilp) { pa = pa + pr[2 * i]; pb = pb + pr[2 * i + 1]; }
+    }
+#pragma unroll
+    for (int v = 0; v < 3; ++v) {
+        if (v < nleft) {
+            const int e0 = 32 * ilp + 8 * v;                  // first element of the leftover vector: 8 elements of one slot
+            const float got = __shfl(rg_pick(pr, e0 >> q.lsh), (e0 & (G - 1)) + (t & 7), G);
+            if (t < 8) pa = pa + got;
+        }
+    }
+    if (q.lsh == 5) {
+        c1 = __shfl(pa, (t & 7) + 8, 32);
+        c2 = __shfl(pa, (t & 7) + 16, 32);
+        c3 = __shfl(pa, (t & 7) + 24, 32);
+    } else {
+        c1 = __shfl(pa, (t & 7) + 8, 16);
+        c2 = __shfl(pb, (t & 7), 16);
+        c3 = __shfl(pb, (t & 7) + 8, 16);
+    }
+    const float r = ((pa + c1) + c2) + c3;                    // meaningful on lanes t < 8
+    float acc = 0.0f;
+#pragma unroll
+    for (int v = 0; v < 7; ++v) {
+        if (v < ntail) {
+            const int e = vec * 8 + v;
+            acc = acc + __shfl(rg_pick(pr, e >> q.lsh), e & (G - 1), G);
+        }
+    }
+#pragma unroll
+    for (int l = 0; l < 8; ++l) acc = acc + __shfl(r, l, G);
+    return acc;
+}
+
+// butterflies over the lanes that share a sample: `width` = the group (a group per row) or the wave (a wave per row)
+__device__ __forceinline__ float rg_wave_min(int width, float a)
+{
+    for (int off = width >> 1; off > 0; off >>= 1) a = fminf(a, __shfl_xor(a, off, 64));
+    return a;
+}
+__device__ __forceinline__ float rg_wave_sum(int width, float a)
+{
+    for (int off = width >> 1; off > 0; off >>= 1) a = a + __shfl_xor(a, off, 64);
+    return a;
 }
 
 // host side

@@ -213,25 +213,41 @@ def init_table(num_nodes: int, dim: int, init_scale: float, seed: int, device) -
 
 def fit_graph_embedding(graph, dim: int, *, epochs: int, batch_size: int = 1024, num_negatives: int = 50, lr: float = 0.3,
                         burn_in_epochs: int = 0, burn_in_factor: float = 0.1, optimizer: str = "rsgd", init_scale: float = 1e-3,
-                        seed: int = 0, c: float = 1.0, device=None, log_every: int = 0) -> GraphEmbeddingResult:
+                        seed: int = 0, c: float = 1.0, device=None, log_every: int = 0, objective: str = "softmax",
+                        margin: float = 0.01, aperture_k: float = 0.1, closure: bool = False) -> GraphEmbeddingResult:
     """Embed ``graph`` (as ``GraphPaths`` accepts it) in ``dim`` hyperbolic dimensions.
 
     Positives are every edge in both directions; an epoch visits them in the order of a ``torch.randperm`` under a CPU
     generator seeded by ``seed``, ``batch_size`` at a time; batch number ``step`` (counted from 0 over the whole run) draws
     its negatives with ``NegativeSampler.sample(pairs, step)``.  The first ``burn_in_epochs`` epochs run at
-    ``lr * burn_in_factor``.  The loss of every batch is summed on the device and read back once per epoch."""
+    ``lr * burn_in_factor``.  The loss of every batch is summed on the device and read back once per epoch.
+
+    ``objective="cones"`` trains a directed hierarchy with ``entailment_cones.entailment_cone_loss`` instead (DESIGN.md 5.21;
+    ``margin``, ``aperture_k``; ``c`` is not used, angles do not depend on it).  Positives are the graph's edges as directed
+    pairs, first column the parent, or their transitive closure when ``closure=True``.  The sampler is built on those pairs
+    and stays undirected: a negative is neither an ancestor nor a descendant of its anchor.  Batch ``step`` corrupts the child
+    (``apex="anchor"`` on ``sample(pairs, 2 step)``) and the parent (``apex="partner"`` on ``sample(pairs[:, [1, 0]],
+    2 step + 1)``); the sum of the two losses is stepped once."""
     from ..optim import RiemannianAdam, RiemannianSGD
+    if objective not in ("softmax", "cones"):
+        raise ValueError(f"fit_graph_embedding: objective must be 'softmax' or 'cones', got {objective!r}")
     if optimizer not in ("rsgd", "radam"):
         raise ValueError(f"fit_graph_embedding: optimizer must be 'rsgd' or 'radam', got {optimizer!r}")
     if not (MIN_WIDTH <= dim + 1 <= MAX_WIDTH):
         raise ValueError(f"fit_graph_embedding: dim must lie in {MIN_WIDTH - 1}..{MAX_WIDTH - 1}, got {dim}")
     if epochs < 0 or batch_size < 1:
         raise ValueError("fit_graph_embedding: epochs must be >= 0 and batch_size >= 1")
+    cones = objective == "cones"
+    if cones:
+        from .entailment_cones import directed_pairs, entailment_cone_loss
+        names, _ = _graph_arrays(graph)
+        pairs = directed_pairs(graph, closure)
+        graph = (names, pairs)
     sampler = NegativeSampler(graph, num_negatives, seed=seed, device=device)
     try:
         dev = sampler.device
         e = sampler.edges[sampler.edges[:, 0] != sampler.edges[:, 1]]
-        positives = torch.from_numpy(np.concatenate([e, e[:, ::-1]], 0).copy()).to(dev)
+        positives = torch.from_numpy(np.ascontiguousarray(e) if cones else np.concatenate([e, e[:, ::-1]], 0).copy()).to(dev)
         table = torch.nn.Parameter(init_table(sampler.n, dim, init_scale, seed, dev))
         opt = (RiemannianSGD([table], lr=lr) if optimizer == "rsgd" else RiemannianAdam([table], lr=lr))
         gen = torch.Generator().manual_seed(int(seed))
@@ -243,8 +259,13 @@ def fit_graph_embedding(graph, dim: int, *, epochs: int, batch_size: int = 1024,
             order = torch.randperm(positives.shape[0], generator=gen).to(dev)
             total = torch.zeros((), dtype=torch.float32, device=dev)
             for b0 in range(0, positives.shape[0], batch_size):
-                index = sampler.sample(positives[order[b0:b0 + batch_size]], step)
-                loss = edge_softmax_loss(table, index, c, "sum", validate=False)
+                batch = positives[order[b0:b0 + batch_size]]
+                if cones:
+                    kw = dict(margin=margin, aperture_k=aperture_k, reduction="sum", validate=False)
+                    loss = (entailment_cone_loss(table, sampler.sample(batch, 2 * step), apex="anchor", **kw) +
+                            entailment_cone_loss(table, sampler.sample(batch[:, [1, 0]], 2 * step + 1), apex="partner", **kw))
+                else:
+                    loss = edge_softmax_loss(table, sampler.sample(batch, step), c, "sum", validate=False)
                 opt.zero_grad(set_to_none=True)
                 loss.backward()
                 opt.step()

@@ -9,7 +9,12 @@ epoch) to ``--output-dir``; with ``--eval-pairs N > 0`` also ``distortion_stats.
 sampled pairs; with ``--eval-reconstruction`` also ``reconstruction_stats.json``: ``reconstruction_metrics`` (mean rank and mAP
 of the graph's edges) of the trained table and, under ``"initial"``, of the table training started from; with
 ``--eval-hyperbolicity N > 0`` also ``hyperbolicity_stats.json``: Gromov's delta, its relative form and the curvature estimate
- of the graph metric and of the trained table's distances on the same sample of N nodes.  The reference has no counterpart: it never trains its embeddings.
+ of the graph metric and of the trained table's distances on the same sample of N nodes.
+``--objective cones`` trains a directed hierarchy with the entailment-cone loss instead (an edge's first node is
+the parent; ``--margin``, ``--aperture-k``; ``--closure`` trains on the transitive closure of the edges) and records those
+options in ``train_log.json``; ``--eval-cones`` writes ``cone_stats.json``: ``cone_stats`` of the graph's edges under the
+trained table and, under ``"initial"``, under the table training started from.  The reference has no counterpart: it never
+trains its embeddings.
 """
 from __future__ import annotations
 
@@ -21,6 +26,7 @@ from typing import Dict, List, Tuple
 import torch
 import typer
 
+from hyptokenizer_amd.embedding.entailment_cones import cone_stats, directed_pairs
 from hyptokenizer_amd.embedding.graph_embedding import GraphEmbeddingResult, fit_graph_embedding, init_table
 from hyptokenizer_amd.embedding.graph_metrics import reconstruction_metrics
 from hyptokenizer_amd.embedding.hyperbolicity import curvature_estimate, embedding_hyperbolicity, graph_hyperbolicity
@@ -73,10 +79,13 @@ def train_graph_embeddings(graph_path: str, output_dir: str, dim: int = 10, epoc
                            num_negatives: int = 50, lr: float = 0.3, burn_in_epochs: int = 10, burn_in_factor: float = 0.1,
                            optimizer: str = "rsgd", init_scale: float = 1e-3, seed: int = 0, curvature: float = 1.0,
                            eval_pairs: int = 0, log_every: int = 1, eval_reconstruction: bool = False,
-                           eval_hyperbolicity: int = 0) -> GraphEmbeddingResult:
+                           eval_hyperbolicity: int = 0, objective: str = "softmax", margin: float = 0.01, aperture_k: float = 0.1,
+                           closure: bool = False, eval_cones: bool = False) -> GraphEmbeddingResult:
     graph = load_graph(graph_path)
     params = dict(dim=dim, epochs=epochs, batch_size=batch_size, num_negatives=num_negatives, lr=lr, burn_in_epochs=burn_in_epochs,
                   burn_in_factor=burn_in_factor, optimizer=optimizer, init_scale=init_scale, seed=seed, c=curvature)
+    if objective != "softmax":                                # the log of a softmax run keeps the keys it always had
+        params.update(objective=objective, margin=margin, aperture_k=aperture_k, closure=closure)
     result = fit_graph_embedding(graph, log_every=log_every, **params)
     os.makedirs(output_dir, exist_ok=True)
     torch.save(result.table.cpu(), os.path.join(output_dir, "embeddings.pt"))
@@ -101,6 +110,15 @@ def train_graph_embeddings(graph_path: str, output_dir: str, dim: int = 10, epoc
     if eval_hyperbolicity > 0:
         with open(os.path.join(output_dir, "hyperbolicity_stats.json"), "w") as f:
             json.dump(hyperbolicity_stats(graph, result, eval_hyperbolicity, seed, curvature), f, indent=4)
+    if eval_cones:
+        edges = directed_pairs(graph, closure=False)          # rows: fit_graph_embedding numbers the nodes in the same order
+        stats = cone_stats(result.table, edges, aperture_k=aperture_k)
+        stats["initial"] = cone_stats(init_table(len(result.node_names), dim, init_scale, seed, result.table.device), edges,
+                                      aperture_k=aperture_k)
+        with open(os.path.join(output_dir, "cone_stats.json"), "w") as f:
+            json.dump(stats, f, indent=4)
+        logger.info(f"Cones: mean energy {stats['mean_energy']:.4f} ({stats['share_inside']:.3f} inside) over {stats['num_edges']} "
+                    f"edges, reversed {stats['reversed_mean_energy']:.4f} ({stats['reversed_share_inside']:.3f} inside)")
     return result
 
 
@@ -142,12 +160,18 @@ def main(
     eval_pairs: int = 0,
     eval_reconstruction: bool = False,
     eval_hyperbolicity: int = 0,
+    objective: str = "softmax",
+    margin: float = 0.01,
+    aperture_k: float = 0.1,
+    closure: bool = False,
+    eval_cones: bool = False,
 ) -> None:
     """Train hyperbolic embeddings of a graph."""
     train_graph_embeddings(graph_path=graph_path, output_dir=output_dir, dim=dim, epochs=epochs, batch_size=batch_size,
                            num_negatives=num_negatives, lr=lr, burn_in_epochs=burn_in_epochs, burn_in_factor=burn_in_factor,
                            optimizer=optimizer, init_scale=init_scale, seed=seed, curvature=curvature, eval_pairs=eval_pairs,
-                           eval_reconstruction=eval_reconstruction, eval_hyperbolicity=eval_hyperbolicity)
+                           eval_reconstruction=eval_reconstruction, eval_hyperbolicity=eval_hyperbolicity, objective=objective,
+                           margin=margin, aperture_k=aperture_k, closure=closure, eval_cones=eval_cones)
 
 
 if __name__ == "__main__":

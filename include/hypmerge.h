@@ -666,6 +666,39 @@ int hm_edge_loss_bwd(const float* x_dev, int64_t ld, int64_t table_rows, int d1,
  * partners); d_0 and every u_k are the same bits. */
 int hm_debug_edge_loss_form(int form);
 
+/* ---- entailment cones: a directed hierarchy loss on a Lorentz table ------------------------------------------
+ * The hyperbolic entailment cones of Ganea, Becigneul & Hofmann (ICML 2018) on points of the unit hyperboloid.  x, index and
+ * the rules for indices outside [0, table_rows) are those of hm_edge_loss_fwd: column 0 the anchor, column 1 the positive,
+ * columns 2.. the negatives; a skipped slot and a skipped sample are never dereferenced.  Of a slot's two rows one is the apex
+ * a (the parent), the other the child b: apex_role 0 makes the anchor the apex of every slot (the negatives are corrupted
+ * children), apex_role 1 every partner (the anchor is the child, the negatives corrupted parents).  With
+ *   u = a0 b0 - sum_s a_s b_s and n = sqrt(sum_s a_s^2) in the canonical order,  w = sqrt(u^2 - 1),  A = (b0 - a0 u) / (n w),
+ *   ext = acos(clamp(A, +-(1 - 2^-20))),  aper = asin(min(2 aperture_k / n, 1 - 2^-10)),  m = ext - aper,  E = max(0, m):
+ *   loss[b] = E_0 + sum_{j >= 1 live} max(0, margin - E_j).
+ * A partner that is the anchor itself (same index), a slot with u <= 1 and an apex at the origin (n = 0) are flat: E = 0 and
+ * no gradient; a clamped factor is a constant (at d1 = 2, a line, every A is +-1 and counts as clamped); a negative inside
+ * the cone (m <= 0) contributes margin and no gradient.
+ * Angles do not depend on curvature: there is no c.
+ * hm_cone_loss_fwd writes loss_dev [n] and weights_dev [n, 1 + k, 4] (16-byte aligned), per slot the hinge-scaled
+ * coefficients (alpha, the anchor's e0 factor, nu / n, the partner's e0 factor) of DESIGN.md 5.21, zero for a skipped or
+ * inactive slot: the only state between the two calls.  hm_cone_loss_bwd takes grad_loss_dev [n] and writes the Euclidean
+ * gradient in COO form exactly as hm_edge_loss_bwd does: values_dev [n * (2 + k), d1], coo_dev int64 [n * (2 + k)] = index
+ * with a skipped slot replaced by the anchor (by 0 when the sample is skipped), its value row zero.  Every row is written
+ * once, no atomics: two calls on the same inputs give the same bits.
+ * Engine-independent; errors through hm_last_error(NULL); asynchronous on `stream`.  HM_E_ARG before the device is touched
+ * for a NULL pointer, a misaligned weights_dev, d1 outside 2..129, ld < d1, negative table_rows / n / k, aperture_k not
+ * positive and finite, margin negative or not finite, apex_role other than 0 or 1.  n == 0: HM_OK, no launch.
+ * Replaces: nothing the reference runs (it has no trainer and no directed objective). */
+int hm_cone_loss_fwd(const float* x_dev, int64_t ld, int64_t table_rows, int d1, const int64_t* index_dev, int64_t n, int64_t k,
+                     float aperture_k, float margin, int apex_role, float* loss_dev, float* weights_dev, void* stream);
+int hm_cone_loss_bwd(const float* x_dev, int64_t ld, int64_t table_rows, int d1, const int64_t* index_dev, int64_t n, int64_t k,
+                     float aperture_k, float margin, int apex_role, const float* weights_dev, const float* grad_loss_dev,
+                     float* values_dev, int64_t* coo_dev, void* stream);
+/* Test / tuning hook: the work decomposition of the two calls above from now on -- 0: one lane group per sample, 1: one wave
+ * per sample (the default).  Losses and anchor rows agree to rounding (another order of the sums over the
+ * partners); every slot's coefficients and partner rows are the same bits.  Replaces: nothing the reference runs. */
+int hm_debug_cone_loss_form(int form);
+
 /* ---- Lorentz-centroid pooling of token rows ---------------------------------------------------------------
  * Serves embedding.pooling.lorentz_centroid / HyperbolicEmbeddingBag and HyperbolicTokenizer.embed_batch: one point of the
  * hyperboloid per line from the rows of its tokens (Law et al., ICML 2019).  x [table_rows, ld] fp32 points of the unit
