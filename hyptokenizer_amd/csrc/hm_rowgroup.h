@@ -17,9 +17,7 @@
 // dereferenced, reads as (dead_t, 0, .., 0) and takes part in butterflies only.  rg_gather is the flight of such rows; two
 // kernels (edge-loss forward, pooling backward) keep theirs written out for speed.  A kernel that walks gathered rows
 // is launched in one of two forms (rg_split_map): a group per row, or a wave per row whose S groups share the walk and
-// fold their partial sums across the wave (rg_fold_groups).  The two losses on an index [rows, 2 + K] (hm_edgeloss.hip,
-// hm_cones.hip) share rg_sample, the anchor / positive test of an index row, and rg_canon_sum, the sum of a row's products
-// in ATen's order on the group's slots, with the butterflies over a sample's lanes (rg_wave_min, rg_wave_sum).
+// fold their partial sums across the wave (rg_fold_groups).
 #pragma once
 #include "hm_common.h"
 
@@ -164,24 +162,6 @@ __device__ __forceinline__ void rg_fold_groups(int lsh, int S, RgRow& v)
 #pragma unroll
         for (int j = 0; j < 4; ++j) v.s[j] = v.s[j] + __shfl_xor(v.s[j], off, 64);
     }
-}
-
-// the sample of this group in an index [rows, 2 + K] (anchor, positive, K negatives): its anchor and whether it is served --
-// a sample whose anchor or positive lies outside [0, V) is not
-struct RgSample {
-    const int64_t* ix;
-    int64_t iu;
-    bool ok;
-};
-
-__device__ __forceinline__ RgSample rg_sample(const int64_t* __restrict__ index, int K, int64_t V, const RgMap& q)
-{
-    RgSample s;
-    s.ix = index + q.row * (int64_t)(2 + K);
-    s.iu = q.live ? s.ix[0] : -1;
-    const int64_t iv = q.live ? s.ix[1] : -1;
-    s.ok = q.live && rg_in(s.iu, V) && rg_in(iv, V);
-    return s;
 }
 
 __device__ __forceinline__ float rg_pick(const float (&p)[4], int j) { return j == 0 ? p[0] : j == 1 ? p[1] : j == 2 ? p[2] : p[3]; }

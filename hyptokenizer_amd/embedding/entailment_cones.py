@@ -32,13 +32,14 @@ from typing import Dict
 
 import numpy as np
 import torch
-from torch.autograd.function import once_differentiable
 
-from .. import _lib
-from ..engine import _f, _ptr, _require_cuda, _stream_of
-from .graph_embedding import MAX_WIDTH, MIN_WIDTH, _graph_arrays, _ld
+from ..engine import _f, _require_cuda
+from ._index_loss import check_index, forward, index_loss
+from ._table import check_table
+from .graph_embedding import _graph_arrays
 
 ROLES = {"anchor": 0, "partner": 1}
+_FWD, _BWD, _SLOT = "hm_cone_loss_fwd", "hm_cone_loss_bwd", (4,)
 
 
 def _check_args(who: str, table: torch.Tensor, index: torch.Tensor, margin: float, aperture_k: float, apex: str, reduction: str,
@@ -49,60 +50,12 @@ def _check_args(who: str, table: torch.Tensor, index: torch.Tensor, margin: floa
         raise ValueError(f"{who}: reduction must be 'mean', 'sum' or 'none', got {reduction!r}")
     if apex not in ROLES:
         raise ValueError(f"{who}: apex must be 'anchor' or 'partner', got {apex!r}")
-    if table.dtype != torch.float32:
-        raise ValueError(f"{who}: the table must be float32, got {table.dtype}")
-    if table.dim() != 2 or not (MIN_WIDTH <= table.shape[1] <= MAX_WIDTH):
-        raise ValueError(f"{who}: the table must be [V, d + 1] with d + 1 in {MIN_WIDTH}..{MAX_WIDTH}, got shape {tuple(table.shape)}")
-    if table.shape[1] > 1 and table.stride(1) != 1 or (table.shape[0] > 1 and table.stride(0) < table.shape[1]):
-        raise ValueError(f"{who}: the table needs unit stride in its last dimension (strides {table.stride()})")
-    if index.dtype != torch.int64:
-        raise ValueError(f"{who}: index must be int64, got {index.dtype}")
-    if index.dim() != 2 or index.shape[1] < 2:
-        raise ValueError(f"{who}: index must be [B, 2 + K] (anchor, positive, K negatives), got shape {tuple(index.shape)}")
+    check_table(who, table)
+    check_index(who, index)
     if not (float(aperture_k) > 0.0 and np.isfinite(float(aperture_k))):
         raise ValueError(f"{who}: aperture_k must be positive and finite, got {aperture_k}")
     if not (float(margin) >= 0.0 and np.isfinite(float(margin))):
         raise ValueError(f"{who}: margin must be non-negative and finite, got {margin}")
-
-
-def _forward(x: torch.Tensor, index: torch.Tensor, margin: float, aperture_k: float, role: int):
-    L = _lib.load()
-    b, k = index.shape[0], index.shape[1] - 2
-    loss = torch.empty(b, dtype=torch.float32, device=x.device)
-    weights = torch.empty((b, 1 + k, 4), dtype=torch.float32, device=x.device)
-    with torch.cuda.device(x.device):
-        _lib.check(L.hm_cone_loss_fwd(_ptr(x), _ld(x), x.shape[0], x.shape[1], _ptr(index), b, k, _f(aperture_k), _f(margin), role,
-                                      _ptr(loss), _ptr(weights), _stream_of(x)))
-    return loss, weights
-
-
-class _ConeLoss(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, table, index, margin: float, aperture_k: float, role: int, sparse_grad: bool):
-        loss, weights = _forward(table.detach(), index, margin, aperture_k, role)
-        ctx.args, ctx.sparse_grad = (float(margin), float(aperture_k), int(role)), bool(sparse_grad)
-        ctx.save_for_backward(table, index, weights)
-        return loss
-
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, g):
-        table, index, weights = ctx.saved_tensors
-        margin, aperture_k, role = ctx.args
-        L = _lib.load()
-        x = table.detach()
-        v, d1 = x.shape
-        b, k = index.shape[0], index.shape[1] - 2
-        g = g.detach().float().contiguous()
-        values = torch.empty((b * (2 + k), d1), dtype=torch.float32, device=x.device)
-        coo = torch.empty(b * (2 + k), dtype=torch.int64, device=x.device)
-        with torch.cuda.device(x.device):
-            _lib.check(L.hm_cone_loss_bwd(_ptr(x), _ld(x), v, d1, _ptr(index), b, k, _f(aperture_k), _f(margin), role, _ptr(weights),
-                                          _ptr(g), _ptr(values), _ptr(coo), _stream_of(x)))
-        grad = torch.sparse_coo_tensor(coo.unsqueeze(0), values, (v, d1), check_invariants=False)
-        if not ctx.sparse_grad:
-            grad = grad.to_dense()
-        return grad, None, None, None, None, None
 
 
 def entailment_cone_loss(table: torch.Tensor, index: torch.Tensor, *, margin: float = 0.01, aperture_k: float = 0.1,
@@ -114,21 +67,8 @@ def entailment_cone_loss(table: torch.Tensor, index: torch.Tensor, *, margin: fl
     ``sparse_grad``, ``validate`` and the COO layout of the gradient are those of ``edge_softmax_loss``: indices
     ``index.reshape(-1)``, a skipped slot replaced by its anchor (by 0 in a skipped sample) with a zero value row."""
     _check_args("entailment_cone_loss", table, index, margin, aperture_k, apex, reduction, sign_convention)
-    _require_cuda(table, index)
-    index = index.contiguous()
-    v = table.shape[0]
-    live = None
-    if validate or reduction == "mean":                      # otherwise nothing but the two kernels and a sum is launched
-        live = ((index[:, :2] >= 0) & (index[:, :2] < v)).all(dim=1)
-    if validate and index.shape[0] > 0 and not bool(live.all()):
-        raise ValueError(f"entailment_cone_loss: an anchor or positive lies outside [0, {v})")
-    loss = _ConeLoss.apply(table, index, float(margin), float(aperture_k), ROLES[apex], bool(sparse_grad))
-    if reduction == "none":
-        return loss
-    total = loss.sum()
-    if reduction == "sum":
-        return total
-    return total / live.sum().clamp(min=1).to(total.dtype)
+    return index_loss("entailment_cone_loss", table, index, _FWD, _BWD, (_f(aperture_k), _f(margin), ROLES[apex]), _SLOT, reduction,
+                      sparse_grad, validate)
 
 
 def cone_energy(table: torch.Tensor, parents: torch.Tensor, children: torch.Tensor, *, aperture_k: float = 0.1) -> torch.Tensor:
@@ -139,7 +79,7 @@ def cone_energy(table: torch.Tensor, parents: torch.Tensor, children: torch.Tens
     index = torch.stack([parents, children], 1)
     _check_args("cone_energy", table, index, 0.0, aperture_k, "anchor", "none", "lorentz")
     _require_cuda(table, index)
-    return _forward(table.detach(), index.contiguous(), 0.0, aperture_k, 0)[0]
+    return forward(_FWD, table.detach(), index.contiguous(), (_f(aperture_k), 0.0, 0), _SLOT)[0]
 
 
 def transitive_closure(n: int, edges) -> np.ndarray:

@@ -26,13 +26,12 @@ from typing import Dict, Hashable, List, Optional, Tuple
 
 import numpy as np
 import torch
-from torch.autograd.function import once_differentiable
 
-from .. import _lib
 from .._handle import DeviceHandle
-from ..engine import _f, _ptr, _require_cuda, _stream_of
+from ..engine import _f, _ptr, _require_cuda
+from ._index_loss import check_index, index_loss
+from ._table import MAX_WIDTH, MIN_WIDTH, check_table, ld as _ld  # noqa: F401  (other modules and tools import them from here)
 
-MIN_WIDTH, MAX_WIDTH = 2, 129
 MAX_NODES = (1 << 31) - 1
 
 
@@ -43,58 +42,10 @@ def _check_loss_args(table: torch.Tensor, index: torch.Tensor, c: float, reducti
                          "every distance is 0 and the loss is constant)")
     if reduction not in ("mean", "sum", "none"):
         raise ValueError(f"edge_softmax_loss: reduction must be 'mean', 'sum' or 'none', got {reduction!r}")
-    if table.dtype != torch.float32:
-        raise ValueError(f"edge_softmax_loss: the table must be float32, got {table.dtype}")
-    if table.dim() != 2 or not (MIN_WIDTH <= table.shape[1] <= MAX_WIDTH):
-        raise ValueError(f"edge_softmax_loss: the table must be [V, d + 1] with d + 1 in {MIN_WIDTH}..{MAX_WIDTH}, got shape "
-                         f"{tuple(table.shape)}")
-    if table.shape[1] > 1 and table.stride(1) != 1 or (table.shape[0] > 1 and table.stride(0) < table.shape[1]):
-        raise ValueError(f"edge_softmax_loss: the table needs unit stride in its last dimension (strides {table.stride()})")
-    if index.dtype != torch.int64:
-        raise ValueError(f"edge_softmax_loss: index must be int64, got {index.dtype}")
-    if index.dim() != 2 or index.shape[1] < 2:
-        raise ValueError(f"edge_softmax_loss: index must be [B, 2 + K] (anchor, positive, K negatives), got shape {tuple(index.shape)}")
+    check_table("edge_softmax_loss", table)
+    check_index("edge_softmax_loss", index)
     if not (float(c) > 0.0 and np.isfinite(float(c))):
         raise ValueError(f"edge_softmax_loss: curvature must be positive and finite, got {c}")
-
-
-def _ld(table: torch.Tensor) -> int:
-    return table.stride(0) if table.shape[0] > 1 else max(table.stride(0), table.shape[1])
-
-
-class _EdgeLoss(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, table, index, c: float, sparse_grad: bool):
-        L = _lib.load()
-        x = table.detach()
-        b, k = index.shape[0], index.shape[1] - 2
-        loss = torch.empty(b, dtype=torch.float32, device=x.device)
-        weights = torch.empty((b, 1 + k), dtype=torch.float32, device=x.device)
-        with torch.cuda.device(x.device):
-            _lib.check(L.hm_edge_loss_fwd(_ptr(x), _ld(x), x.shape[0], x.shape[1], _ptr(index), b, k, _f(c), _ptr(loss),
-                                          _ptr(weights), _stream_of(x)))
-        ctx.c, ctx.sparse_grad = float(c), bool(sparse_grad)
-        ctx.save_for_backward(table, index, weights)
-        return loss
-
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, g):
-        table, index, weights = ctx.saved_tensors
-        L = _lib.load()
-        x = table.detach()
-        v, d1 = x.shape
-        b, k = index.shape[0], index.shape[1] - 2
-        g = g.detach().float().contiguous()
-        values = torch.empty((b * (2 + k), d1), dtype=torch.float32, device=x.device)
-        coo = torch.empty(b * (2 + k), dtype=torch.int64, device=x.device)
-        with torch.cuda.device(x.device):
-            _lib.check(L.hm_edge_loss_bwd(_ptr(x), _ld(x), v, d1, _ptr(index), b, k, _f(ctx.c), _ptr(weights), _ptr(g),
-                                          _ptr(values), _ptr(coo), _stream_of(x)))
-        grad = torch.sparse_coo_tensor(coo.unsqueeze(0), values, (v, d1), check_invariants=False)
-        if not ctx.sparse_grad:
-            grad = grad.to_dense()
-        return grad, None, None, None
 
 
 def edge_softmax_loss(table: torch.Tensor, index: torch.Tensor, c: float = 1.0, reduction: str = "mean", *,
@@ -107,21 +58,8 @@ def edge_softmax_loss(table: torch.Tensor, index: torch.Tensor, c: float = 1.0, 
     ``sparse_grad=False`` lets torch densify it.  ``validate=True`` checks the anchors and positives against ``[0, V)`` with
     one synchronising read and raises ``ValueError``; ``validate=False`` reads nothing back and such samples are skipped."""
     _check_loss_args(table, index, c, reduction, sign_convention)
-    _require_cuda(table, index)
-    index = index.contiguous()
-    v = table.shape[0]
-    live = None
-    if validate or reduction == "mean":                      # otherwise nothing but the two kernels and a sum is launched
-        live = ((index[:, :2] >= 0) & (index[:, :2] < v)).all(dim=1)
-    if validate and index.shape[0] > 0 and not bool(live.all()):
-        raise ValueError(f"edge_softmax_loss: an anchor or positive lies outside [0, {v})")
-    loss = _EdgeLoss.apply(table, index, float(c), bool(sparse_grad))
-    if reduction == "none":
-        return loss
-    total = loss.sum()
-    if reduction == "sum":
-        return total
-    return total / live.sum().clamp(min=1).to(total.dtype)
+    return index_loss("edge_softmax_loss", table, index, "hm_edge_loss_fwd", "hm_edge_loss_bwd", (_f(c),), (), reduction, sparse_grad,
+                      validate)
 
 
 # ---- the sampler ----------------------------------------------------------------------------------------------------------

@@ -37,7 +37,8 @@ import torch
 
 from .. import _lib
 from ..engine import _ptr, _require_cuda, _stream_of
-from .graph_embedding import MAX_NODES, MAX_WIDTH, MIN_WIDTH, _graph_arrays, _ld, sorted_symmetric_csr
+from ._table import check_table, ld as _ld
+from .graph_embedding import MAX_NODES, _graph_arrays, sorted_symmetric_csr
 
 
 @dataclass
@@ -66,12 +67,7 @@ def set_walk_layout(layout: int) -> None:
 
 def _check_count_args(table: torch.Tensor, row_ptr: torch.Tensor, col: torch.Tensor, nodes: Optional[torch.Tensor]) -> None:
     who = "neighbor_rank_counts"
-    if table.dtype != torch.float32:
-        raise ValueError(f"{who}: the table must be float32, got {table.dtype}")
-    if table.dim() != 2 or not (MIN_WIDTH <= table.shape[1] <= MAX_WIDTH):
-        raise ValueError(f"{who}: the table must be [V, d + 1] with d + 1 in {MIN_WIDTH}..{MAX_WIDTH}, got shape {tuple(table.shape)}")
-    if table.stride(1) != 1 or (table.shape[0] > 1 and table.stride(0) < table.shape[1]):
-        raise ValueError(f"{who}: the table needs unit stride in its last dimension (strides {table.stride()})")
+    check_table(who, table)
     v = table.shape[0]
     if not 1 <= v <= MAX_NODES:
         raise ValueError(f"{who}: the table must have between 1 and 2^31 - 1 rows, got {v}")

@@ -30,20 +30,15 @@ from torch.autograd.function import once_differentiable
 
 from .. import _lib
 from ..engine import _ptr, _require_cuda, _stream_of
-from .graph_embedding import MAX_WIDTH, MIN_WIDTH, _ld, init_table
+from ._table import MAX_WIDTH, MIN_WIDTH, check_table, ld as _ld
+from .graph_embedding import init_table
 
 
 def _check_args(table, ids, offsets, lengths, weights, sign_convention: str) -> None:
     if sign_convention != "lorentz":
         raise ValueError(f"lorentz_centroid: sign_convention must be 'lorentz', got {sign_convention!r} (the centroid is "
                          "defined on the hyperboloid x0^2 - |x_s|^2 = 1 only)")
-    if table.dtype != torch.float32:
-        raise ValueError(f"lorentz_centroid: the table must be float32, got {table.dtype}")
-    if table.dim() != 2 or not (MIN_WIDTH <= table.shape[1] <= MAX_WIDTH):
-        raise ValueError(f"lorentz_centroid: the table must be [V, d + 1] with d + 1 in {MIN_WIDTH}..{MAX_WIDTH}, got shape "
-                         f"{tuple(table.shape)}")
-    if table.stride(1) != 1 or (table.shape[0] > 1 and table.stride(0) < table.shape[1]):
-        raise ValueError(f"lorentz_centroid: the table needs unit stride in its last dimension (strides {table.stride()})")
+    check_table("lorentz_centroid", table)
     if ids.dtype != torch.int64 or ids.dim() != 1:
         raise ValueError(f"lorentz_centroid: ids must be int64 [T], got {ids.dtype} {tuple(ids.shape)}")
     if offsets.dtype != torch.int64 or offsets.dim() != 1 or offsets.numel() < 1:

@@ -31,9 +31,8 @@ import math
 import torch
 
 from .. import _lib
+from ..embedding._table import MAX_WIDTH, MIN_WIDTH
 from ..engine import _ptr, _require_cuda, _stream_of
-
-MIN_WIDTH, MAX_WIDTH = 2, 129
 
 
 def _f32(x: float) -> float:

@@ -95,23 +95,28 @@ def bag_shape(n: int, rot: int):
     return lens, [lens[i] + SLACK[(rot + i) % len(SLACK)] for i in range(n)]
 
 
+def index_and_upstream(case, gen) -> dict:
+    """The index [B, 2 + K] and the upstream gradient [B] of a loss on an index (tests/cone_bits_cases.py draws them too)."""
+    b, k = case["B"], case["K"]
+    idx = torch.randint(0, V, (b, 2 + k), generator=gen, dtype=torch.int64)
+    idx[:, 1] = (idx[:, 0] + 1 + torch.randint(0, V - 1, (b,), generator=gen)) % V
+    if k >= 5:
+        idx[::3, 4] = -1
+    if k >= 2 and b >= 3:
+        idx[1, 2] = idx[1, 0]                                   # a negative that is its anchor
+        idx[2, 3] = idx[2, 2]                                   # a repeated negative
+    if case.get("outside"):
+        idx[0, 2], idx[0, 3], idx[0, 5] = -1, V + 2, idx[0, 0]
+        idx[1, 0] = V                                           # the anchor outside: the sample is skipped
+        idx[2, 1] = -5                                          # the positive outside: the sample is skipped
+    return {"index": idx, "g": (0.5 + torch.rand(b, generator=gen, dtype=torch.float64)).float()}
+
+
 def inputs(case) -> dict:
     gen = torch.Generator().manual_seed(_seed(case))
     x = _table(case["d1"], gen)
     if case["fam"] == "edge":
-        b, k = case["B"], case["K"]
-        idx = torch.randint(0, V, (b, 2 + k), generator=gen, dtype=torch.int64)
-        idx[:, 1] = (idx[:, 0] + 1 + torch.randint(0, V - 1, (b,), generator=gen)) % V
-        if k >= 5:
-            idx[::3, 4] = -1
-        if k >= 2 and b >= 3:
-            idx[1, 2] = idx[1, 0]                               # a negative that is its anchor
-            idx[2, 3] = idx[2, 2]                               # a repeated negative
-        if case.get("outside"):
-            idx[0, 2], idx[0, 3], idx[0, 5] = -1, V + 2, idx[0, 0]
-            idx[1, 0] = V                                       # the anchor outside: the sample is skipped
-            idx[2, 1] = -5                                      # the positive outside: the sample is skipped
-        return {"x": x, "index": idx, "g": (0.5 + torch.rand(b, generator=gen, dtype=torch.float64)).float()}
+        return {"x": x, **index_and_upstream(case, gen)}
     n = case["n"]
     lens, span = bag_shape(n, case["rot"])
     offsets = torch.zeros(n + 1, dtype=torch.int64)
