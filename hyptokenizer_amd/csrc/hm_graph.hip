@@ -21,7 +21,7 @@
 // Components: min-label propagation with hooking and pointer jumping.  labels[v] starts at v, only decreases, and is
 // always a node of v's component, so concurrent atomicMin updates can only change how fast the fixed point is reached,
 // not what it is: every node carries the smallest index of its component.
-#include "hm_table.h"
+#include "hm_csr.h"
 
 #define HM_GRAPH_MAX_NODES ((int64_t)1 << 24)
 #define HM_GRAPH_BITS_BUDGET ((int64_t)1 << 30)
@@ -38,11 +38,9 @@ struct GraphCtl {
 
 struct hm_graph {
     int device = 0;
-    int64_t n = 0, nnz = 0;
+    HmCsr csr;
     int64_t pass_words_cap = 0;                  // knob graph_pass_words (0: the memory bound alone)
     int64_t chunk_levels = 16;                   // knob graph_chunk_levels
-    DevBuf<int64_t> d_row;
-    DevBuf<int32_t> d_col;
     DevBuf<unsigned long long> d_bits;           // seen | frontier | next, n * W words each
     DevBuf<int32_t> d_idx;                       // staging: seeds, sorted pairs, column nodes
     DevBuf<GraphCtl> d_ctl;
@@ -241,7 +239,7 @@ __global__ __launch_bounds__(HM_GRAPH_THREADS) void hm_graph_roots_kernel(int64_
 int hm_graph_check(hm_graph* g, const char* who, bool need_csr)
 {
     if (!g) return hm_fail(nullptr, HM_E_ARG, std::string(who) + ": NULL handle");
-    if (need_csr && g->n <= 0) return hm_fail(nullptr, HM_E_STATE, std::string(who) + ": no graph set (hm_graph_set_csr)");
+    if (need_csr && g->csr.n <= 0) return hm_fail(nullptr, HM_E_STATE, std::string(who) + ": no graph set (hm_graph_set_csr)");
     return HM_OK;
 }
 
@@ -249,7 +247,7 @@ int hm_graph_check(hm_graph* g, const char* who, bool need_csr)
 int64_t hm_graph_words(const hm_graph* g, int64_t sources)
 {
     int64_t W = std::max<int64_t>(1, (sources + 63) / 64);
-    W = std::min(W, std::max<int64_t>(1, HM_GRAPH_BITS_BUDGET / (24 * g->n)));
+    W = std::min(W, std::max<int64_t>(1, HM_GRAPH_BITS_BUDGET / (24 * g->csr.n)));
     if (g->pass_words_cap > 0) W = std::min(W, g->pass_words_cap);
     return W;
 }
@@ -275,7 +273,7 @@ int hm_graph_get_ctl(hm_graph* g, hipStream_t s)
 template <class Second>
 int hm_graph_bfs(hm_graph* g, const int32_t* seeds_dev, int64_t count, int W, hipStream_t s, Second second)
 {
-    const int64_t total = g->n * W;
+    const int64_t total = g->csr.n * W;
     unsigned long long* seen = g->d_bits.p;
     unsigned long long* fr = seen + total;
     unsigned long long* nx = fr + total;
@@ -283,11 +281,11 @@ int hm_graph_bfs(hm_graph* g, const int32_t* seeds_dev, int64_t count, int W, hi
     hipLaunchKernelGGL(hm_graph_seed_kernel, dim3(hm_blocks(count, HM_GRAPH_THREADS)), dim3(HM_GRAPH_THREADS), 0, s, seeds_dev, count, W, seen, fr);
     second(fr, (int64_t)0);
     g->last_launches += 2;
-    for (int64_t L = 1; L <= g->n;) {
-        const int64_t end = std::min(g->n, L + g->chunk_levels - 1);
+    for (int64_t L = 1; L <= g->csr.n;) {
+        const int64_t end = std::min(g->csr.n, L + g->chunk_levels - 1);
         for (; L <= end; ++L) {
-            hipLaunchKernelGGL(hm_graph_pull_kernel, dim3(hm_blocks(total, HM_GRAPH_THREADS)), dim3(HM_GRAPH_THREADS), 0, s, g->d_row.p,
-                               g->d_col.p, total, W, fr, seen, nx, g->d_ctl.p, L);
+            hipLaunchKernelGGL(hm_graph_pull_kernel, dim3(hm_blocks(total, HM_GRAPH_THREADS)), dim3(HM_GRAPH_THREADS), 0, s, g->csr.row.p,
+                               g->csr.col.p, total, W, fr, seen, nx, g->d_ctl.p, L);
             second(nx, L);
             std::swap(fr, nx);
             g->last_launches += 2;
@@ -336,26 +334,8 @@ extern "C" int hm_graph_destroy(hm_graph* g)
 extern "C" int hm_graph_set_csr(hm_graph* g, const int64_t* row_ptr, const int32_t* col, int64_t n, void* stream)
 {
     if (int rc = hm_graph_check(g, "hm_graph_set_csr", false)) return rc;
-    if (!row_ptr || n < 1 || n > HM_GRAPH_MAX_NODES) return hm_fail(nullptr, HM_E_ARG, "hm_graph_set_csr: n must lie in [1, 2^24]");
-    if (row_ptr[0] != 0) return hm_fail(nullptr, HM_E_ARG, "hm_graph_set_csr: row_ptr[0] must be 0");
-    for (int64_t v = 0; v < n; ++v)
-        if (row_ptr[v + 1] < row_ptr[v] || row_ptr[v + 1] >= ((int64_t)1 << 31))
-            return hm_fail(nullptr, HM_E_ARG, "hm_graph_set_csr: row_ptr must not decrease and nnz must stay below 2^31");
-    const int64_t nnz = row_ptr[n];
-    if (nnz > 0 && !col) return hm_fail(nullptr, HM_E_ARG, "hm_graph_set_csr: col is NULL");
-    for (int64_t e = 0; e < nnz; ++e)
-        if (col[e] < 0 || (int64_t)col[e] >= n) return hm_fail(nullptr, HM_E_ARG, "hm_graph_set_csr: column index out of range");
-    HM_HIP0(hipSetDevice(g->device));
-    hipStream_t s = (hipStream_t)stream;
-    g->n = 0;
-    HM_HIP0(g->d_row.alloc(n + 1));
-    HM_HIP0(g->d_col.alloc(nnz));
-    HM_HIP0(hipMemcpyAsync(g->d_row.p, row_ptr, sizeof(int64_t) * (size_t)(n + 1), hipMemcpyHostToDevice, s));
-    if (nnz > 0) HM_HIP0(hipMemcpyAsync(g->d_col.p, col, sizeof(int32_t) * (size_t)nnz, hipMemcpyHostToDevice, s));
-    HM_HIP0(hipStreamSynchronize(s));       // pageable caller memory
-    g->n = n;
-    g->nnz = nnz;
-    return HM_OK;
+    if (int rc = hm_csr_check("hm_graph_set_csr", row_ptr, col, n, HM_GRAPH_MAX_NODES, "[1, 2^24]", false)) return rc;
+    return hm_csr_set(g->csr, g->device, row_ptr, col, n, (hipStream_t)stream);
 }
 
 extern "C" int hm_graph_components(hm_graph* g, int32_t* labels_dev, int64_t* n_components, void* stream)
@@ -365,16 +345,16 @@ extern "C" int hm_graph_components(hm_graph* g, int32_t* labels_dev, int64_t* n_
     HM_HIP0(hipSetDevice(g->device));
     hipStream_t s = (hipStream_t)stream;
     hm_graph_begin(g, 0);
-    const dim3 grid(hm_blocks(g->n, HM_GRAPH_THREADS)), block(HM_GRAPH_THREADS);
+    const dim3 grid(hm_blocks(g->csr.n, HM_GRAPH_THREADS)), block(HM_GRAPH_THREADS);
     if (int rc = hm_graph_put_ctl(g, 1, s)) return rc;
-    hipLaunchKernelGGL(hm_graph_iota_kernel, grid, block, 0, s, labels_dev, g->n);
+    hipLaunchKernelGGL(hm_graph_iota_kernel, grid, block, 0, s, labels_dev, g->csr.n);
     g->last_launches += 1;
     // an iteration that changes nothing ends the loop; every other one lowers a label, so n + 1 iterations bound it
-    for (int64_t it = 0; it <= g->n;) {
-        const int64_t end = std::min(g->n, it + 3);
+    for (int64_t it = 0; it <= g->csr.n;) {
+        const int64_t end = std::min(g->csr.n, it + 3);
         for (; it <= end; ++it) {
-            hipLaunchKernelGGL(hm_graph_prop_kernel, grid, block, 0, s, g->d_row.p, g->d_col.p, g->n, labels_dev, g->d_ctl.p, it);
-            hipLaunchKernelGGL(hm_graph_jump_kernel, grid, block, 0, s, g->n, labels_dev, g->d_ctl.p, it);
+            hipLaunchKernelGGL(hm_graph_prop_kernel, grid, block, 0, s, g->csr.row.p, g->csr.col.p, g->csr.n, labels_dev, g->d_ctl.p, it);
+            hipLaunchKernelGGL(hm_graph_jump_kernel, grid, block, 0, s, g->csr.n, labels_dev, g->d_ctl.p, it);
             g->last_launches += 2;
         }
         HM_HIP0(hipGetLastError());
@@ -382,7 +362,7 @@ extern "C" int hm_graph_components(hm_graph* g, int32_t* labels_dev, int64_t* n_
         if (g->h_ctl.p[1].stop != 0) break;
     }
     if (g->h_ctl.p[1].stop == 0) return hm_fail(nullptr, HM_E_STATE, "hm_graph_components: no fixed point (internal error)");
-    hipLaunchKernelGGL(hm_graph_roots_kernel, grid, block, 0, s, g->n, labels_dev, g->d_ctl.p);
+    hipLaunchKernelGGL(hm_graph_roots_kernel, grid, block, 0, s, g->csr.n, labels_dev, g->d_ctl.p);
     g->last_launches += 1;
     HM_HIP0(hipGetLastError());
     if (int rc = hm_graph_get_ctl(g, s)) return rc;
@@ -398,7 +378,7 @@ extern "C" int hm_graph_pair_lengths(hm_graph* g, const int32_t* src, const int3
     if (n_pairs < 0 || n_pairs >= ((int64_t)1 << 31) || (n_pairs > 0 && (!src || !dst || !out_dev)))
         return hm_fail(nullptr, HM_E_ARG, "hm_graph_pair_lengths: bad arguments");
     for (int64_t p = 0; p < n_pairs; ++p)
-        if (src[p] < 0 || src[p] >= g->n || dst[p] < 0 || dst[p] >= g->n)
+        if (src[p] < 0 || src[p] >= g->csr.n || dst[p] < 0 || dst[p] >= g->csr.n)
             return hm_fail(nullptr, HM_E_ARG, "hm_graph_pair_lengths: node index out of range");
     hm_graph_begin(g, 0);
     if (n_pairs == 0) return HM_OK;
@@ -430,7 +410,7 @@ extern "C" int hm_graph_pair_lengths(hm_graph* g, const int32_t* src, const int3
         st_pair[i] = (int32_t)p;
     }
     HM_HIP0(g->d_idx.grow((int64_t)stage.size()));
-    if (g->d_bits.cap < 3 * g->n * W) HM_HIP0(g->d_bits.alloc(3 * g->n * W));      // exactly the bound, never grow()'s doubling
+    if (g->d_bits.cap < 3 * g->csr.n * W) HM_HIP0(g->d_bits.alloc(3 * g->csr.n * W));      // exactly the bound, never grow()'s doubling
     HM_HIP0(hipMemcpyAsync(g->d_idx.p, stage.data(), sizeof(int32_t) * stage.size(), hipMemcpyHostToDevice, s));
     HM_HIP0(hipMemsetAsync(out_dev, 0xff, sizeof(int32_t) * (size_t)n_pairs, s));
     const int32_t* d_slot = g->d_idx.p + S;
@@ -457,13 +437,13 @@ extern "C" int hm_graph_distance_rows(hm_graph* g, const int32_t* src, int64_t n
                                       int64_t ld, void* stream)
 {
     if (int rc = hm_graph_check(g, "hm_graph_distance_rows", true)) return rc;
-    const int64_t M = cols ? n_cols : g->n;
+    const int64_t M = cols ? n_cols : g->csr.n;
     if (n_src < 0 || n_src >= ((int64_t)1 << 31) || M < 0 || (n_src > 0 && !src) || ld < M || (n_src > 0 && M > 0 && !out_dev))
         return hm_fail(nullptr, HM_E_ARG, "hm_graph_distance_rows: bad arguments");
     for (int64_t k = 0; k < n_src; ++k)
-        if (src[k] < 0 || src[k] >= g->n) return hm_fail(nullptr, HM_E_ARG, "hm_graph_distance_rows: source index out of range");
+        if (src[k] < 0 || src[k] >= g->csr.n) return hm_fail(nullptr, HM_E_ARG, "hm_graph_distance_rows: source index out of range");
     for (int64_t m = 0; cols && m < M; ++m)
-        if (cols[m] < 0 || cols[m] >= g->n) return hm_fail(nullptr, HM_E_ARG, "hm_graph_distance_rows: column index out of range");
+        if (cols[m] < 0 || cols[m] >= g->csr.n) return hm_fail(nullptr, HM_E_ARG, "hm_graph_distance_rows: column index out of range");
     hm_graph_begin(g, 0);
     if (n_src == 0 || M == 0) return HM_OK;
     HM_HIP0(hipSetDevice(g->device));
@@ -471,7 +451,7 @@ extern "C" int hm_graph_distance_rows(hm_graph* g, const int32_t* src, int64_t n
     const int64_t W = hm_graph_words(g, n_src), per_pass = 64 * W;
     g->last_words = W;
     HM_HIP0(g->d_idx.grow(n_src + (cols ? M : 0)));
-    if (g->d_bits.cap < 3 * g->n * W) HM_HIP0(g->d_bits.alloc(3 * g->n * W));      // exactly the bound, never grow()'s doubling
+    if (g->d_bits.cap < 3 * g->csr.n * W) HM_HIP0(g->d_bits.alloc(3 * g->csr.n * W));      // exactly the bound, never grow()'s doubling
     HM_HIP0(hipMemcpyAsync(g->d_idx.p, src, sizeof(int32_t) * (size_t)n_src, hipMemcpyHostToDevice, s));
     if (cols) HM_HIP0(hipMemcpyAsync(g->d_idx.p + n_src, cols, sizeof(int32_t) * (size_t)M, hipMemcpyHostToDevice, s));
     const int32_t* d_cols = cols ? g->d_idx.p + n_src : nullptr;

@@ -6,16 +6,14 @@
 // seed, counter = (sample b, slot k, attempt t, step), candidate = (uint64(r) * V) >> 32 from the first output word r.  A
 // slot is a pure function of (seed, step, b, k, anchor): no state, no dependence on the launch geometry.  A rejected
 // candidate is redrawn with the next t; after max_tries rejections the slot is -1, the loss kernels' mask.
-#include "hm_table.h"
+#include "hm_csr.h"
 
 #define HM_NS_THREADS 256
 #define HM_NS_MAX_NODES (((int64_t)1 << 31) - 1)
 
 struct hm_negsample {
     int device = 0;
-    int64_t n = 0, nnz = 0;
-    DevBuf<int64_t> d_row;
-    DevBuf<int32_t> d_col;
+    HmCsr csr;
 };
 
 namespace {
@@ -89,37 +87,14 @@ extern "C" int hm_negsample_destroy(hm_negsample* g)
 // The host-side checks of hm_negsample_set_csr, apart from the handle: what the kernel's indexing relies on.
 extern "C" int hm_negsample_check_csr(const int64_t* row_ptr, const int32_t* col, int64_t n)
 {
-    if (!row_ptr || n < 1 || n > HM_NS_MAX_NODES) return hm_fail(nullptr, HM_E_ARG, "hm_negsample_set_csr: n must lie in [1, 2^31)");
-    if (row_ptr[0] != 0) return hm_fail(nullptr, HM_E_ARG, "hm_negsample_set_csr: row_ptr[0] must be 0");
-    for (int64_t v = 0; v < n; ++v)
-        if (row_ptr[v + 1] < row_ptr[v] || row_ptr[v + 1] >= ((int64_t)1 << 31))
-            return hm_fail(nullptr, HM_E_ARG, "hm_negsample_set_csr: row_ptr must not decrease and nnz must stay below 2^31");
-    if (row_ptr[n] > 0 && !col) return hm_fail(nullptr, HM_E_ARG, "hm_negsample_set_csr: col is NULL");
-    for (int64_t v = 0; v < n; ++v)
-        for (int64_t e = row_ptr[v]; e < row_ptr[v + 1]; ++e) {
-            if (col[e] < 0 || (int64_t)col[e] >= n) return hm_fail(nullptr, HM_E_ARG, "hm_negsample_set_csr: column index out of range");
-            if (e > row_ptr[v] && col[e] <= col[e - 1])
-                return hm_fail(nullptr, HM_E_ARG, "hm_negsample_set_csr: a row must be sorted and free of repeats");
-        }
-    return HM_OK;
+    return hm_csr_check("hm_negsample_set_csr", row_ptr, col, n, HM_NS_MAX_NODES, "[1, 2^31)", true);
 }
 
 extern "C" int hm_negsample_set_csr(hm_negsample* g, const int64_t* row_ptr, const int32_t* col, int64_t n, void* stream)
 {
     if (!g) return hm_fail(nullptr, HM_E_ARG, "hm_negsample_set_csr: NULL handle");
     if (int rc = hm_negsample_check_csr(row_ptr, col, n)) return rc;
-    const int64_t nnz = row_ptr[n];
-    HM_HIP0(hipSetDevice(g->device));
-    hipStream_t s = (hipStream_t)stream;
-    g->n = 0;
-    HM_HIP0(g->d_row.alloc(n + 1));
-    HM_HIP0(g->d_col.alloc(nnz));
-    HM_HIP0(hipMemcpyAsync(g->d_row.p, row_ptr, sizeof(int64_t) * (size_t)(n + 1), hipMemcpyHostToDevice, s));
-    if (nnz > 0) HM_HIP0(hipMemcpyAsync(g->d_col.p, col, sizeof(int32_t) * (size_t)nnz, hipMemcpyHostToDevice, s));
-    HM_HIP0(hipStreamSynchronize(s));                         // pageable caller memory
-    g->n = n;
-    g->nnz = nnz;
-    return HM_OK;
+    return hm_csr_set(g->csr, g->device, row_ptr, col, n, (hipStream_t)stream);
 }
 
 extern "C" int hm_negsample_sample(hm_negsample* g, const int64_t* pairs_dev, int64_t n_pairs, int64_t k, uint64_t seed, int64_t step,
@@ -129,12 +104,12 @@ extern "C" int hm_negsample_sample(hm_negsample* g, const int64_t* pairs_dev, in
     if (n_pairs < 0 || n_pairs > ((int64_t)1 << 31) || k < 0 || k > ((int64_t)1 << 20) || step < 0 || step >= ((int64_t)1 << 32) ||
         max_tries < 1 || max_tries > 65536 || (n_pairs + 1) * (k + 2) > ((int64_t)1 << 38) || (n_pairs > 0 && (!pairs_dev || !out_dev)))
         return hm_fail(nullptr, HM_E_ARG, "hm_negsample_sample: bad arguments");
-    if (g->n <= 0) return hm_fail(nullptr, HM_E_STATE, "hm_negsample_sample: no graph set (hm_negsample_set_csr)");
+    if (g->csr.n <= 0) return hm_fail(nullptr, HM_E_STATE, "hm_negsample_sample: no graph set (hm_negsample_set_csr)");
     if (n_pairs == 0) return HM_OK;
     HM_HIP0(hipSetDevice(g->device));
     const int64_t total = n_pairs * (2 + k);
-    hipLaunchKernelGGL(hm_ns_kernel, dim3(hm_blocks(total, HM_NS_THREADS)), dim3(HM_NS_THREADS), 0, (hipStream_t)stream, g->d_row.p, g->d_col.p,
-                       g->n, pairs_dev, n_pairs, k, (uint32_t)seed, (uint32_t)(seed >> 32), (uint32_t)step, max_tries, out_dev);
+    hipLaunchKernelGGL(hm_ns_kernel, dim3(hm_blocks(total, HM_NS_THREADS)), dim3(HM_NS_THREADS), 0, (hipStream_t)stream, g->csr.row.p, g->csr.col.p,
+                       g->csr.n, pairs_dev, n_pairs, k, (uint32_t)seed, (uint32_t)(seed >> 32), (uint32_t)step, max_tries, out_dev);
     HM_HIP0(hipGetLastError());
     return HM_OK;
 }

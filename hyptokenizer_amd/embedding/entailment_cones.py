@@ -34,9 +34,9 @@ import numpy as np
 import torch
 
 from ..engine import _f, _require_cuda
+from ..graph import Graph
 from ._index_loss import check_index, forward, index_loss
 from ._table import check_table
-from .graph_embedding import _graph_arrays
 
 ROLES = {"anchor": 0, "partner": 1}
 _FWD, _BWD, _SLOT = "hm_cone_loss_fwd", "hm_cone_loss_bwd", (4,)
@@ -90,13 +90,12 @@ def transitive_closure(n: int, edges) -> np.ndarray:
     A host routine: one breadth-first search per node over a CSR of the out-edges, O(n (n + E)) time in the worst case and
     O(n + E) memory beside the M pairs of the result -- meant for taxonomies (WordNet's noun closure has 7 * 10^5 pairs), not
     for dense graphs."""
-    edges = np.asarray(edges, dtype=np.int64).reshape(-1, 2)
-    if n < 0 or (edges.size and (edges.min() < 0 or edges.max() >= n)):
-        raise ValueError(f"transitive_closure: an edge names a node outside [0, {n})")
-    order = np.argsort(edges[:, 0], kind="stable")
-    col = edges[order, 1]
-    row_ptr = np.zeros(n + 1, np.int64)
-    np.cumsum(np.bincount(edges[:, 0], minlength=n), out=row_ptr[1:])
+    return _closure(Graph(range(n), np.asarray(edges, dtype=np.int64).reshape(-1, 2), "transitive_closure"))
+
+
+def _closure(graph: Graph) -> np.ndarray:
+    n = graph.n
+    row_ptr, col = graph.out_csr()
     out = []
     seen = np.zeros(n, bool)
     for root in range(n):
@@ -132,6 +131,5 @@ def cone_stats(table: torch.Tensor, edges, *, aperture_k: float = 0.1) -> Dict[s
 def directed_pairs(graph, closure: bool) -> np.ndarray:
     """The positives of ``fit_graph_embedding(objective="cones")``: the graph's edges as (parent, child) rows, self-loops
     dropped, or their transitive closure."""
-    names, edges = _graph_arrays(graph)
-    edges = edges[edges[:, 0] != edges[:, 1]]
-    return transitive_closure(len(names), edges) if closure else edges
+    g = Graph.of(graph, "directed_pairs")
+    return _closure(g) if closure else g.edges[g.edges[:, 0] != g.edges[:, 1]]

@@ -20,19 +20,17 @@ There is no CPU fallback: off a HIP device the functions raise ``HypMergeUnavail
 """
 from __future__ import annotations
 
-import ctypes as C
 from dataclasses import dataclass, field
-from typing import Dict, Hashable, List, Optional, Tuple
+from typing import Dict, Hashable, List
 
 import numpy as np
 import torch
 
-from .._handle import DeviceHandle
 from ..engine import _f, _ptr, _require_cuda
+# noqa below: other modules, tests and tools import these names from here
+from ..graph import MAX_SAMPLER_NODES as MAX_NODES, Graph, GraphHandle, graph_arrays as _graph_arrays, sorted_symmetric_csr  # noqa: F401
 from ._index_loss import check_index, index_loss
-from ._table import MAX_WIDTH, MIN_WIDTH, check_table, ld as _ld  # noqa: F401  (other modules and tools import them from here)
-
-MAX_NODES = (1 << 31) - 1
+from ._table import MAX_WIDTH, MIN_WIDTH, check_table, ld as _ld  # noqa: F401
 
 
 # ---- the loss -------------------------------------------------------------------------------------------------------------
@@ -63,60 +61,22 @@ def edge_softmax_loss(table: torch.Tensor, index: torch.Tensor, c: float = 1.0, 
 
 
 # ---- the sampler ----------------------------------------------------------------------------------------------------------
-def _graph_arrays(graph) -> Tuple[List[Hashable], np.ndarray]:
-    """(node names in index order, edges int64 [E, 2]) of a graph as ``GraphPaths`` accepts it."""
-    if isinstance(graph, tuple) and len(graph) == 2:
-        names, edges = list(graph[0]), np.asarray(graph[1], dtype=np.int64)
-        if edges.ndim == 2 and edges.shape[1] != 2 and edges.shape[0] == 2:
-            edges = edges.T
-        return names, edges.reshape(-1, 2)
-    names = list(graph.nodes())
-    index = {name: k for k, name in enumerate(names)}
-    return names, np.array([(index[e[0]], index[e[1]]) for e in graph.edges()], dtype=np.int64).reshape(-1, 2)
-
-
-def sorted_symmetric_csr(n: int, edges: np.ndarray) -> Tuple[np.ndarray, np.ndarray]:
-    """(row_ptr int64[n + 1], col int32[nnz]) of the undirected graph: both directions of every edge, every row sorted and
-    free of repeats, self-loops dropped (the sampler rejects the anchor itself anyway)."""
-    edges = np.asarray(edges, dtype=np.int64).reshape(-1, 2)
-    if edges.size and (edges.min() < 0 or edges.max() >= n):
-        raise ValueError(f"NegativeSampler: an edge names a node outside [0, {n})")
-    edges = edges[edges[:, 0] != edges[:, 1]]
-    key = np.unique(np.concatenate([edges[:, 0] * n + edges[:, 1], edges[:, 1] * n + edges[:, 0]]))
-    row_ptr = np.zeros(n + 1, np.int64)
-    np.cumsum(np.bincount(key // n, minlength=n), out=row_ptr[1:])
-    return row_ptr, np.ascontiguousarray((key % n).astype(np.int32))
-
-
-class NegativeSampler(DeviceHandle):
+class NegativeSampler(GraphHandle):
     """``num_negatives`` nodes per (anchor, positive) pair, uniform over ``[0, V)`` except the anchor and its neighbours, from
     Philox4x32-10 keyed by ``seed`` with counter (sample, slot, attempt, step): ``sample(pairs, step)`` is a pure function
     of its arguments and ``seed``, whatever the device does.  A slot whose ``max_tries`` candidates were all rejected is
     ``-1``, the mask of ``edge_softmax_loss``.  ``graph`` is as ``GraphPaths`` accepts it."""
 
     PREFIX = "hm_negsample"
+    CANONICAL = True
+    NODE_LIMIT, NODE_LIMIT_TEXT = MAX_NODES, "2^31 - 1"
 
     def __init__(self, graph, num_negatives: int, seed: int = 0, device=None, max_tries: int = 32):
-        names, edges = _graph_arrays(graph)
-        self.n = len(names)
-        if self.n < 1:
-            raise ValueError("NegativeSampler: a graph without nodes")
-        if self.n > MAX_NODES:
-            raise ValueError(f"NegativeSampler: {self.n} nodes, the limit is 2^31 - 1")
         if num_negatives < 0 or not (1 <= max_tries <= 65536):
             raise ValueError("NegativeSampler: num_negatives must be >= 0 and max_tries in 1..65536")
         self.num_negatives, self.max_tries = int(num_negatives), int(max_tries)
         self.seed = int(seed) & ((1 << 64) - 1)
-        self.node_names: List[Hashable] = names
-        self.index: Dict[Hashable, int] = {name: k for k, name in enumerate(names)}
-        self.edges = edges
-        row_ptr, col = sorted_symmetric_csr(self.n, edges)
-        if device is None:
-            device = "cuda" if torch.cuda.is_available() else "cpu"
-        super().__init__(device)
-        self.nnz = int(row_ptr[-1])
-        self._check(self._L.hm_negsample_set_csr(self._h, C.c_void_p(row_ptr.ctypes.data), C.c_void_p(col.ctypes.data), self.n,
-                                                 self._stream()))
+        super().__init__(graph, device)
 
     def sample(self, pairs: torch.Tensor, step: int) -> torch.Tensor:
         """``pairs`` int64 ``[B, 2]`` on the sampler's device -> ``index`` int64 ``[B, 2 + num_negatives]``."""
@@ -176,11 +136,10 @@ def fit_graph_embedding(graph, dim: int, *, epochs: int, batch_size: int = 1024,
     if epochs < 0 or batch_size < 1:
         raise ValueError("fit_graph_embedding: epochs must be >= 0 and batch_size >= 1")
     cones = objective == "cones"
+    graph = Graph.of(graph, "NegativeSampler")
     if cones:
         from .entailment_cones import directed_pairs, entailment_cone_loss
-        names, _ = _graph_arrays(graph)
-        pairs = directed_pairs(graph, closure)
-        graph = (names, pairs)
+        graph = Graph(graph.node_names, directed_pairs(graph, closure))
     sampler = NegativeSampler(graph, num_negatives, seed=seed, device=device)
     try:
         dev = sampler.device

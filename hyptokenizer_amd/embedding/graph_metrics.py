@@ -37,8 +37,8 @@ import torch
 
 from .. import _lib
 from ..engine import _ptr, _require_cuda, _stream_of
+from ..graph import MAX_SAMPLER_NODES as MAX_NODES, Graph, select_nodes, sorted_symmetric_csr
 from ._table import check_table, ld as _ld
-from .graph_embedding import MAX_NODES, _graph_arrays, sorted_symmetric_csr
 
 
 @dataclass
@@ -80,11 +80,7 @@ def _check_count_args(table: torch.Tensor, row_ptr: torch.Tensor, col: torch.Ten
     if nodes is not None:
         if nodes.dtype != torch.int64 or nodes.dim() != 1:
             raise ValueError(f"{who}: nodes must be int64 [n], got {nodes.dtype} {tuple(nodes.shape)}")
-        if nodes.numel() > 0:
-            if int(nodes.min()) < 0 or int(nodes.max()) >= v:
-                raise ValueError(f"{who}: nodes names a row outside [0, {v})")
-            if int(torch.unique(nodes).numel()) != nodes.numel():
-                raise ValueError(f"{who}: nodes must be free of repeats")
+        select_nodes(nodes, v, who, what="row")
 
 
 def neighbor_rank_counts(table: torch.Tensor, row_ptr: torch.Tensor, col: torch.Tensor, nodes: Optional[torch.Tensor] = None, *,
@@ -172,13 +168,11 @@ def reconstruction_metrics(table: torch.Tensor, graph, *, node_mapping: Optional
     if sign_convention != "lorentz":
         raise ValueError(f"reconstruction_metrics: sign_convention must be 'lorentz', got {sign_convention!r} (under 'reference' "
                          "every distance is 0 and every rank is 1)")
-    names, edges = _graph_arrays(graph)
-    n = len(names)
+    g = Graph.of(graph, "reconstruction_metrics")
+    names, edges, n = g.node_names, g.edges, g.n
     if table.dim() != 2:
         raise ValueError(f"reconstruction_metrics: the table must be [V, d + 1], got shape {tuple(table.shape)}")
     v = table.shape[0]
-    if edges.size and (edges.min() < 0 or edges.max() >= n):
-        raise ValueError(f"reconstruction_metrics: an edge names a node outside [0, {n})")
     if node_mapping is None:
         if n != v:
             raise ValueError(f"reconstruction_metrics: the graph has {n} nodes and the table {v} rows; pass node_mapping")
@@ -194,11 +188,7 @@ def reconstruction_metrics(table: torch.Tensor, graph, *, node_mapping: Optional
             raise ValueError("reconstruction_metrics: node_mapping sends two nodes to one row")
         edges = rows[edges] if edges.size else edges
     if nodes is not None:
-        sel = torch.as_tensor(nodes).detach().cpu().reshape(-1).numpy().astype(np.int64)
-        if sel.size and (sel.min() < 0 or sel.max() >= n):
-            raise ValueError(f"reconstruction_metrics: nodes names a node outside [0, {n})")
-        if np.unique(sel).size != sel.size:
-            raise ValueError("reconstruction_metrics: nodes must be free of repeats")
+        sel = g.select(nodes, "reconstruction_metrics")
         sel = sel if rows is None else rows[sel]
     elif rows is not None:
         sel = rows
@@ -206,7 +196,7 @@ def reconstruction_metrics(table: torch.Tensor, graph, *, node_mapping: Optional
         sel = None
     _check_count_args(table, torch.empty(v + 1, dtype=torch.int64), torch.empty(0, dtype=torch.int32), None)
     _require_cuda(table)
-    row_ptr, col = sorted_symmetric_csr(v, edges)
+    row_ptr, col = g.csr(True) if rows is None else sorted_symmetric_csr(v, edges)
     dev = table.device
     counts = neighbor_rank_counts(table, torch.from_numpy(row_ptr).to(dev), torch.from_numpy(col).to(dev),
                                   None if sel is None else torch.from_numpy(np.ascontiguousarray(sel)).to(dev), validate=False)

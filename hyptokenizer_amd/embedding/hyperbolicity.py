@@ -32,6 +32,7 @@ import torch
 
 from .. import _lib
 from ..engine import _ptr, _require_cuda, _stream_of
+from ..graph import select_nodes
 from ..graph_paths import GraphPaths
 from . import lorentz_model
 
@@ -156,14 +157,7 @@ def graph_hyperbolicity(graph_or_paths, nodes=None, num_samples: int = 2048, bas
     in the kept sample.  ``delta`` is exact for the sample and the bases, in units of half an edge."""
     paths = graph_or_paths if isinstance(graph_or_paths, GraphPaths) else GraphPaths(graph_or_paths)
     rng = np.random.default_rng(seed)
-    if nodes is None:
-        pool = np.arange(paths.n, dtype=np.int64)
-    else:
-        pool = torch.as_tensor(nodes).detach().cpu().reshape(-1).numpy().astype(np.int64)
-        if pool.size and (pool.min() < 0 or pool.max() >= paths.n):
-            raise ValueError(f"graph_hyperbolicity: nodes names a node outside [0, {paths.n})")
-        if np.unique(pool).size != pool.size:
-            raise ValueError("graph_hyperbolicity: nodes must be free of repeats")
+    pool = np.arange(paths.n, dtype=np.int64) if nodes is None else paths.graph.select(nodes, "graph_hyperbolicity")
     if pool.size == 0 or num_samples < 1:
         raise ValueError("graph_hyperbolicity: nothing to sample")
     sample = _draw(rng, pool, min(int(num_samples), MAX_POINTS))
@@ -190,14 +184,7 @@ def embedding_hyperbolicity(table: torch.Tensor, nodes=None, num_samples: int = 
         raise ValueError("embedding_hyperbolicity: the table must be a float32 matrix [V, d + 1]")
     v = int(table.shape[0])
     rng = np.random.default_rng(seed)
-    if nodes is None:
-        pool = np.arange(v, dtype=np.int64)
-    else:
-        pool = torch.as_tensor(nodes).detach().cpu().reshape(-1).numpy().astype(np.int64)
-        if pool.size and (pool.min() < 0 or pool.max() >= v):
-            raise ValueError(f"embedding_hyperbolicity: nodes names a row outside [0, {v})")
-        if np.unique(pool).size != pool.size:
-            raise ValueError("embedding_hyperbolicity: nodes must be free of repeats")
+    pool = np.arange(v, dtype=np.int64) if nodes is None else select_nodes(nodes, v, "embedding_hyperbolicity", what="row")
     if pool.size == 0 or num_samples < 1:
         raise ValueError("embedding_hyperbolicity: nothing to sample")
     _require_cuda(table)

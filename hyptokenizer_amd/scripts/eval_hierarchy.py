@@ -34,6 +34,7 @@ import torch
 import typer
 
 from hyptokenizer_amd.embedding.lorentz_model import batch_distance, distance
+from hyptokenizer_amd.graph import Graph
 from hyptokenizer_amd.graph_paths import GraphPaths
 
 logging.basicConfig(level=logging.INFO, format="%(asctime)s - %(name)s - %(levelname)s - %(message)s")
@@ -66,7 +67,7 @@ def create_node_mapping(graph, vocab: List[str]) -> Dict[str, int]:
     for k, token in enumerate(vocab):
         first.setdefault(token, k)
     mapping: Dict[str, int] = {}
-    nodes = list(graph.nodes())
+    nodes = Graph.of(graph).node_names
     for node in nodes:
         k = first.get(node.split(".")[0])
         if k is not None:
@@ -203,7 +204,7 @@ def evaluate_hierarchy(embeddings_path: str, vocab_path: str, graph_path: str, o
     with open(vocab_path, "r") as f:
         vocab = json.load(f)
     logger.info(f"Loaded vocabulary with {len(vocab)} tokens")
-    graph = load_wordnet_graph(graph_path)
+    graph = Graph.of(load_wordnet_graph(graph_path))
     node_mapping = create_node_mapping(graph, vocab)
     ratios, stats = compute_distortion(graph=graph, embeddings=embeddings, node_mapping=node_mapping, num_pairs=num_pairs,
                                        curvature=curvature, device=device, sign_convention=sign_convention)

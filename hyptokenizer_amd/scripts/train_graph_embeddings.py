@@ -21,7 +21,7 @@ from __future__ import annotations
 import json
 import logging
 import os
-from typing import Dict, List, Tuple
+from typing import Dict
 
 import torch
 import typer
@@ -30,6 +30,7 @@ from hyptokenizer_amd.embedding.entailment_cones import cone_stats, directed_pai
 from hyptokenizer_amd.embedding.graph_embedding import GraphEmbeddingResult, fit_graph_embedding, init_table
 from hyptokenizer_amd.embedding.graph_metrics import reconstruction_metrics
 from hyptokenizer_amd.embedding.hyperbolicity import curvature_estimate, embedding_hyperbolicity, graph_hyperbolicity
+from hyptokenizer_amd.graph import Graph
 from hyptokenizer_amd.graph_paths import GraphPaths
 from hyptokenizer_amd.scripts.eval_hierarchy import compute_distortion, load_wordnet_graph, set_seeds
 
@@ -37,24 +38,10 @@ logging.basicConfig(level=logging.INFO, format="%(asctime)s - %(name)s - %(level
 logger = logging.getLogger(__name__)
 
 
-class EdgeListGraph:
-    """The two methods ``GraphPaths`` and ``NegativeSampler`` ask of a graph, over a list of named edges."""
-
-    def __init__(self, edges: List[Tuple[str, str]]):
-        self._edges = list(edges)
-        self._nodes: Dict[str, None] = {}
-        for a, b in self._edges:
-            self._nodes.setdefault(a)
-            self._nodes.setdefault(b)
-
-    def nodes(self):
-        return list(self._nodes)
-
-    def edges(self):
-        return list(self._edges)
+EdgeListGraph = Graph.from_named_edges                      # a list of (name, name) edges -> Graph
 
 
-def load_edge_list(path: str) -> EdgeListGraph:
+def load_edge_list(path: str) -> Graph:
     """One edge per line, two node names separated by a tab; empty lines and lines starting with ``#`` are skipped."""
     edges = []
     with open(path, "r", encoding="utf-8") as f:
@@ -66,13 +53,14 @@ def load_edge_list(path: str) -> EdgeListGraph:
             if len(parts) != 2 or not parts[0] or not parts[1]:
                 raise ValueError(f"{path}:{no}: expected two tab-separated node names")
             edges.append((parts[0], parts[1]))
-    return EdgeListGraph(edges)
+    return Graph.from_named_edges(edges)
 
 
-def load_graph(graph_path: str):
+def load_graph(graph_path: str) -> Graph:
+    """Normalised once: training and every evaluation below share the one ``Graph`` and the CSR forms it keeps."""
     if graph_path.endswith((".tsv", ".txt")):
         return load_edge_list(graph_path)
-    return load_wordnet_graph(graph_path)
+    return Graph.of(load_wordnet_graph(graph_path))
 
 
 def train_graph_embeddings(graph_path: str, output_dir: str, dim: int = 10, epochs: int = 50, batch_size: int = 1024,
