@@ -228,7 +228,7 @@ struct hm_engine {
     unsigned long long scan_tag = 0;      // launch tags of the item queue (monotonic per engine)
     std::map<const void*, int> scan_slots; // resident blocks per scan kernel instantiation on this engine's device
     int head = HM_SCAN_HEAD;              // knob `head`: k-steps of the argmin scan's head test (hm_head_steps); 0 = the kernels without it
-    int head_ring = HM_SCAN_HEAD_RING_DEFAULT;   // knob `head_ring`: the head kernels' partner-tile ring (kScanRings, hm_scan_geom.h; 0 = the ring of every other kernel)
+    int head_ring = HM_SCAN_HEAD_RING_DEFAULT;   // knobs `head_ring` (0 .. 2) and `head_blocks` (3: ring 3): the head kernels' partner-tile ring (kScanRings, hm_scan_geom.h; 0 = the ring of every other kernel)
     int head_span = HM_SCAN_HEAD_SPAN_DEFAULT;   // knob `head_span`: ring slots the head kernels compute per barrier (ScanRun, hm_scan_geom.h; 1 or 2; ring 0 has span 1)
     int64_t argmin_col_begin = 0;         // knob `argmin_col_begin` (tests): hm_pairwise_argmin only looks at partners j >= this (a fresh engine: the seed knows nothing of it)
     bool head_force = false;              // knob `head_force` (tests): every eligible argmin launch takes the head kernel, whatever hm_head_live expects

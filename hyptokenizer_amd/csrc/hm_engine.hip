@@ -44,7 +44,7 @@ extern "C" int hm_abi_version(void) { return HM_ABI_VERSION; }
 // ---- work-decomposition knobs (test / tuning hook: hm_debug_set_knob, hm_debug_set_default_knob) ----
 #if defined(HM_TUNING)
 static const char* const kKnobNames[] = {"chunk", "tail", "tail_div", "big_rows", "shape", "incr_topk", "kc_even", "phases", "ph_share0", "ph_share1", "ph_share2", "ph_share3", "ph_share4",
-                                        "ph_div1", "ph_div2", "ph_div3", "ph_div4", "ph_div5", "pipeline", "pipe_fault_at", "pipeline_pairs", "dyn", "dyn_slots", "head", "head_force", "head_ring", "head_span", "argmin_col_begin"};
+                                        "ph_div1", "ph_div2", "ph_div3", "ph_div4", "ph_div5", "pipeline", "pipe_fault_at", "pipeline_pairs", "dyn", "dyn_slots", "head", "head_force", "head_ring", "head_blocks", "head_span", "argmin_col_begin"};
 #endif
 static std::map<std::string, double> g_default_knobs;          // applied to every engine created afterwards
 
@@ -63,7 +63,10 @@ static int hm_apply_knob(hm_engine* e, const char* name, double v)
     else if (k == "dyn_slots") { if (!(v >= 0 && v <= 65536)) return HM_E_ARG; e->dyn_slots = (int)v; }
     else if (k == "head") { if (!(v == 0.0 || v == (double)HM_SCAN_HEAD)) return HM_E_ARG; e->head = (int)v; }      // argmin scan, bf16 form: 0 = no head test
     else if (k == "head_force") e->head_force = v != 0.0;
-    else if (k == "head_ring") { if (!(v >= 0 && v < HM_SCAN_RINGS && v == (double)(int)v)) return HM_E_ARG; e->head_ring = (int)v; }   // head kernels: ring geometry (kScanRings)
+    // head kernels: ring geometry (kScanRings).  `head_ring` names the two-blocks-per-CU rings 0 .. 2, as it always has; the
+    // three-blocks-per-CU ring (ring 3, the default) has its own knob: `head_blocks` 3 selects it, 2 the ring it replaced (ring 1)
+    else if (k == "head_ring") { if (!(v >= 0 && v < HM_SCAN_RINGS_TWO_BLOCK && v == (double)(int)v)) return HM_E_ARG; e->head_ring = (int)v; }
+    else if (k == "head_blocks") { if (!(v == 2.0 || v == 3.0)) return HM_E_ARG; e->head_ring = v == 3.0 ? 3 : 1; }
     else if (k == "head_span") { if (!(v == 1.0 || v == 2.0)) return HM_E_ARG; e->head_span = (int)v; }      // head kernels: ring slots per barrier (ScanRun)
     else if (k == "argmin_col_begin") { if (!(v >= 0)) return HM_E_ARG; e->argmin_col_begin = (int64_t)v; }      // test hook: hm_pairwise_argmin over partners j >= this
     // test hook, a question and no setting: HM_E_STATE unless the word the head kernels raise on a loose bound (HostCtl::head_bad) is (v != 0)

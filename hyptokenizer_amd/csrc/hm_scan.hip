@@ -101,8 +101,15 @@ __device__ __forceinline__ void hm_dma_run(const char* src, uint32_t dst)
 // front of the barrier that frees it; what changes is the grain of everything paid per barrier: one request of two slots,
 // one counted wait, one fresh group and one reduction outside the MFMAs' shadow per 128 columns, and for tiles right of
 // the block's rows a straight-line body (head_tile_lean).  The key load of a tile is picked up behind that tile's own wait.
+//
+// RING = 3 (head kernels at span 2; kScanRings::blocks = 3): THREE blocks per CU, three waves per SIMD.  The LDS is the ring's
+// four exact slots and the queue word -- no slack: the slot-by-slot walk takes its groups one at a time and requests no
+// fragment behind a slot's last group -- and the kernel is built for at most 168 VGPRs.  Every tile's wait is a vmcnt(0) (ScanRun:
+// nothing stays in flight behind it), so the two asynchronous results need no fixed registers: they are ordinary loads the
+// compiler sees, issued ahead of the tile's requests, and in/out operands of the wait statement.  Whatever copy the compiler
+// makes of them, it makes behind a wait of its own for the load, and that wait can only fall where the tile waits anyway.
 template <int NG, int SIGN, int MODE, int BF, int TM, int WPB, int SUB, bool WK = false, int HEAD = 0, int RING = 0, int SPAN = 1>
-__global__ __launch_bounds__(64 * WPB, 2) void hm_scan_kernel(const ScanArgs p)
+__global__ __launch_bounds__(64 * WPB, (HEAD > 0 && kScanRings[RING].blocks == 3) ? 3 : 2) void hm_scan_kernel(const ScanArgs p)
 {
     static_assert(SUB % 2 == 0, "the two accumulator sets alternate between column groups: an even number per tile");
     static_assert(RING == 0 || HEAD > 0, "rings other than 0 belong to the head kernels");
@@ -110,6 +117,9 @@ __global__ __launch_bounds__(64 * WPB, 2) void hm_scan_kernel(const ScanArgs p)
     // the geometry of this instantiation (hm_scan_geom.h: sizes, ring, LDS map)
     using G = ScanGeom<NG, BF, TM, WPB, SUB, RING, SPAN>;
     static_assert(G::SPAN == SPAN, "a span the ring has no slots for is the dispatch's to replace (hm_launch_scan_ng)");
+    static_assert(G::RING == RING, "a ring the width or the span has no room for is the dispatch's to replace (hm_launch_scan_ng)");
+    constexpr bool TRI = (G::BLOCKS == 3);         // three blocks per CU: no slack behind the ring, no fixed registers
+    static_assert(!TRI || (HEAD > 0 && SPAN == 2), "the three-block ring is the span-2 head kernels'");
     constexpr int COLS = G::COLS, RS = G::RS, RB16 = G::RB16, TILE_BYTES = G::TILE_BYTES, NP = G::NP;
     constexpr int PPW = G::PPW, TILE_LDS = G::TILE_LDS, DIST = G::DIST, NBUF = G::NBUF;
     constexpr int RSUB = G::RSUB;                  // 32-column groups per ring slot (SUB: per tile of the item plan)
@@ -655,7 +665,24 @@ __global__ __launch_bounds__(64 * WPB, 2) void hm_scan_kernel(const ScanArgs p)
     // head k-steps carry the reduction of group g - 1's head values, whose test follows.  Nothing is pending behind the slot
     // (the recomputation of a failed group reads its columns from the slot): the last group is reduced on its own.
     auto head_walk = [&](int buf, int j0) __attribute__((always_inline)) {
-        if constexpr (HEAD > 0) {
+        if constexpr (TRI) {
+            // three blocks per CU: the slot's groups one by one in one accumulator set, each fresh, reduced and tested before
+            // the next starts.  These are the diagonal tiles, the waves without rows and a run's odd end -- a hundredth of the
+            // tiles at 50 000 rows --, and this way no finished group waits in the other set while a failed one is recomputed
+            // (32 accumulator and 12 fragment registers fewer at the kernel's widest point), and no fragment is requested
+            // behind a slot's last group: the ring has no slack for such a request to land in
+#pragma unroll 1
+            for (int sub = 0; sub < RSUB; ++sub) {
+                const int j0s = j0 + sub * 32;
+                if (!(wave_active && (j0s + 31 > i0w))) continue;
+                const char* bt = head_at(buf, sub);
+                float ext_u = 0.0f;
+                head_group(std::integral_constant<int, 0>{}, std::false_type{}, std::false_type{}, bt, bt, true, ext_u);
+                ext_u = reduce_group(std::integral_constant<int, 0>{});
+                ++hg_tot;
+                hc_tot += head_finish(std::integral_constant<int, 0>{}, ext_u, buf, sub, j0s) ? 1 : 0;
+            }
+        } else if constexpr (HEAD > 0) {
             bool hp = false;
             int hg = 0, hc = 0;          // groups of this slot that ran / that had to be recomputed
 #pragma unroll 1
@@ -813,9 +840,23 @@ __global__ __launch_bounds__(64 * WPB, 2) void hm_scan_kernel(const ScanArgs p)
             // the running key every 8th tile (128 columns: a plan tile), into its fixed registers (see the span-1 walk below);
             // issued ahead of the tile's requests, so the tile's own wait covers it (ScanRun)
             const bool poll = (k & 7) == 0;
+            unsigned long long k_raw = ~0ull, d_raw = 0ull;      // TRI: this tile's key load and queue draw
+            if constexpr (TRI) {
+                // (compiler-visible loads; picked up as operands of the tile's vmcnt(0) below)
+                if (poll) k_raw = __hip_atomic_load(&p.ctr64[1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                if (dyn && last && threadIdx.x == 0) {
+                    // (the address through a vector register: hipcc rewrites an atomic on a wave-uniform address into one per
+                    // wave whose result it broadcasts at once -- a wait for the draw right here, in front of the tile)
+                    uint64_t qa = reinterpret_cast<uint64_t>(p.q_ctr);
+                    asm volatile("" : "+v"(qa));
+                    d_raw = __hip_atomic_fetch_add(reinterpret_cast<__attribute__((address_space(1))) unsigned long long*>(qa), 1ull, __ATOMIC_RELAXED,
+                                                   __HIP_MEMORY_SCOPE_AGENT);      // (a global atomic: a flat one would count as an LDS access too)
+                }
+            } else {
             if (poll) asm volatile("global_load_dwordx2 v[252:253], %0, off sc1" : : "v"(&p.ctr64[1]) : "memory", "v252", "v253");
             if (dyn && last && threadIdx.x == 0)
                 asm volatile("global_atomic_add_x2 v[254:255], %0, %1, off sc0" : : "v"(p.q_ctr), "v"(1ull) : "memory", "v254", "v255");
+            }
             {
                 const int rq = run.req_first(k), nrq = run.req_count(k);
                 const int bq = ring_add(buf, NBUF - SPAN);
@@ -829,6 +870,12 @@ __global__ __launch_bounds__(64 * WPB, 2) void hm_scan_kernel(const ScanArgs p)
 #pragma unroll 1
                 for (int sl = 0; sl < nslot; ++sl) head_walk(sl ? buf1 : buf, j0 + sl * COLS);
             }
+            if constexpr (TRI) {
+                // nothing of the run stays in flight behind a tile of this ring (ScanRun::outstanding_max = 0)
+                asm volatile("s_waitcnt vmcnt(0)" : "+v"(k_raw), "+v"(d_raw) : : "memory");
+                if (k_raw < gk) gk = k_raw;                     // the key only ever decreases (~0 where the tile did not poll)
+                if (dyn && last && threadIdx.x == 0) { qslot[0] = (uint32_t)d_raw; qslot[1] = (uint32_t)(d_raw >> 32); }
+            } else {
             ring_wait(run.outstanding(k));
             if (poll) {
                 uint32_t klo, khi;
@@ -840,6 +887,7 @@ __global__ __launch_bounds__(64 * WPB, 2) void hm_scan_kernel(const ScanArgs p)
                 uint32_t qlo, qhi;
                 asm volatile("v_mov_b32 %0, v254\n\tv_mov_b32 %1, v255" : "=v"(qlo), "=v"(qhi) : : "memory", "v254", "v255");
                 qslot[0] = qlo; qslot[1] = qhi;
+            }
             }
             __syncthreads();                                 // every wave's pieces have landed; all reads of the tile's slots done
             buf = ring_add(buf, SPAN);
@@ -1042,6 +1090,7 @@ static hipError_t hm_launch_scan_t(hm_engine* e, const ScanArgs& a, dim3 grid, h
     using G = ScanGeom<NG, BF, TM, WPB, SUB, RING, SPAN>;
     const size_t lds = G::lds_bytes(MODE);
     static_assert(RING == 0 || G::lds_bytes(MODE) <= HM_LDS_PER_BLOCK, "a deeper ring keeps two blocks per CU");
+    static_assert(G::BLOCKS != 3 || 3 * hm_lds_alloc(G::lds_bytes(MODE)) <= HM_LDS_PER_CU, "a three-block ring keeps three");
     const void* fn = reinterpret_cast<const void*>(&hm_scan_kernel<NG, SIGN, MODE, BF, TM, WPB, SUB, WK, HEAD, RING, SPAN>);
     if (lds > 48 * 1024 && e->attr_done.find(fn) == e->attr_done.end()) {     // per engine (= per device), not process-wide
         hipError_t st = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
@@ -1093,13 +1142,15 @@ static hipError_t hm_launch_scan_ng(hm_engine* e, int sign, int mode, const Scan
                     // geometry's to replace (ScanGeom::SPAN): that launch takes the ring's span-1 kernel
 #define HM_HEAD_RING_CASE(R, S)                                                                                            \
     case 4 * S + R: {                                                                                                      \
-        constexpr int SP = ScanGeom<NG, BF, TM, WPB, SUB, R, S>::SPAN;                                                     \
-        if (a.key_wide) return hm_launch_scan_t<NG, 1, HM_MODE_ARGMIN, BF, TM, WPB, SUB, true, HD, R, SP>(e, a, grid, s, ev0, ev1); \
-        return hm_launch_scan_t<NG, 1, HM_MODE_ARGMIN, BF, TM, WPB, SUB, false, HD, R, SP>(e, a, grid, s, ev0, ev1);       \
+        constexpr int RG = ScanGeom<NG, BF, TM, WPB, SUB, R, S>::RING, SP = ScanGeom<NG, BF, TM, WPB, SUB, R, S>::SPAN; \
+        if (a.key_wide) return hm_launch_scan_t<NG, 1, HM_MODE_ARGMIN, BF, TM, WPB, SUB, true, HD, RG, SP>(e, a, grid, s, ev0, ev1); \
+        return hm_launch_scan_t<NG, 1, HM_MODE_ARGMIN, BF, TM, WPB, SUB, false, HD, RG, SP>(e, a, grid, s, ev0, ev1);      \
     }
-                    static_assert(HM_SCAN_RINGS == 3, "one case per ring and span");
+                    // (ring 3 is ring 1 with span 1 and at the widths where three blocks do not fit a CU: ScanGeom::RING)
+                    static_assert(HM_SCAN_RINGS == 4, "one case per ring and span");
                     switch (4 * (e->head_ring == 0 ? 1 : e->head_span) + e->head_ring) {      // (ring 0 ignores the span)
-                        HM_HEAD_RING_CASE(0, 1) HM_HEAD_RING_CASE(1, 1) HM_HEAD_RING_CASE(2, 1) HM_HEAD_RING_CASE(1, 2) HM_HEAD_RING_CASE(2, 2)
+                        HM_HEAD_RING_CASE(0, 1) HM_HEAD_RING_CASE(1, 1) HM_HEAD_RING_CASE(2, 1) HM_HEAD_RING_CASE(3, 1)
+                        HM_HEAD_RING_CASE(1, 2) HM_HEAD_RING_CASE(2, 2) HM_HEAD_RING_CASE(3, 2)
                     }
 #undef HM_HEAD_RING_CASE
                     return hipErrorInvalidValue;

@@ -64,7 +64,7 @@ HM_HOST_DEVICE_INLINE constexpr int hm_shape_rows_max(int shape = 0)
 }
 static_assert(hm_shape_rows_max() == HM_MAX_BLOCK_ROWS, "the images are allocated with one largest block of slack rows");
 
-// ---- partner-tile rings: index = the kernels' RING argument, entry = {sub, dist, exact}.  A ring slot holds `sub`
+// ---- partner-tile rings: index = the kernels' RING argument, entry = {sub, dist, exact, blocks}.  A ring slot holds `sub`
 // 32-column groups (0: the kernel's SUB), `dist` tiles are in flight ahead of the computed one (0: HM_DIST_BF16 / 1), and
 // with `exact` every wave moves its exact share of the tile's pieces and a slot is as large as the tile (otherwise every
 // wave moves PPW pieces and the slot is padded to PPW * WPB KiB).  Ring 0 is every kernel's but the head kernels' of the
@@ -73,12 +73,23 @@ static_assert(hm_shape_rows_max() == HM_MAX_BLOCK_ROWS, "the images are allocate
 // (hm_scan_plan.h) stays 32 * SUB columns for every ring; a kernel with narrower slots walks an item's run in its own tiles.
 //   1  64-column slots padded to 16 KiB: 4 slots, 3 tiles (40 KB at 13 chunks) in flight
 //   2  64-column slots of the tile's own 13 KiB: 5 slots, 4 tiles (53 KB) in flight
-struct ScanRing { int sub, dist, exact; };
-#define HM_SCAN_RINGS 3
-constexpr ScanRing kScanRings[HM_SCAN_RINGS] = {{0, 0, 0}, {2, 3, 0}, {2, 4, 1}};
+//   3  64-column slots of the tile's own size, four of them and no slack region behind them (`blocks` = 3): 52 KiB + the
+//      queue word at 13 chunks, so that THREE blocks share a CU -- its kernels are built for three waves per SIMD.  Defined
+//      for span 2 and for the widths at which three blocks fit (2, 4, 8 and 13 chunks); asked for at another width or with
+//      span 1 it IS ring 1 (ScanGeom::RING, a constant of the instantiation: nothing is decided at run time)
+struct ScanRing { int sub, dist, exact, blocks; };     // blocks: resident blocks per CU the LDS map is cut for (0: two, with the slack region)
+#define HM_SCAN_RINGS 4
+#define HM_SCAN_RINGS_TWO_BLOCK 3      // rings 0 .. 2, the values of the knob `head_ring`; ring 3 is the knob `head_blocks` = 3
+constexpr ScanRing kScanRings[HM_SCAN_RINGS] = {{0, 0, 0, 0}, {2, 3, 0, 0}, {2, 4, 1, 0}, {2, 3, 1, 3}};
+#define HM_LDS_PER_CU (160 * 1024)
+#define HM_LDS_GRANULE 1280            // a block's LDS is allocated in units of this many bytes
+HM_HOST_DEVICE_INLINE constexpr int hm_lds_alloc(int bytes) { return (bytes + HM_LDS_GRANULE - 1) / HM_LDS_GRANULE * HM_LDS_GRANULE; }
 // the head kernels' ring (knob `head_ring`).  Measured at 50 000 rows, interleaved in one process (profiles/scan_head_ring_ab.json):
-// ring 1 takes 2.5 - 4 % off the scan launch of ring 0; ring 2 -- a third more in flight and no padding traffic -- none
-#define HM_SCAN_HEAD_RING_DEFAULT 1
+// ring 1 takes 2.5 - 4 % off the scan launch of ring 0; ring 2 -- a third more in flight and no padding traffic -- none.
+// Ring 3 (three blocks per CU), interleaved with ring 1 x span 2 and with the parent's library (profiles/scan_head_ring3_ab.json):
+// 4 % off the scan launch at 50 000 rows and 7 % at 100 000 in every run; level at 30 000 and 40 000, 1 - 4 % behind at 20 000
+// and 70 000 (the item list's phases were cut for 512 resident blocks, not 768)
+#define HM_SCAN_HEAD_RING_DEFAULT 3
 // slots the head kernels compute per barrier (knob `head_span`; ring 0 has none to choose).  Measured at 50 000 and 100 000
 // rows, interleaved in one process (profiles/scan_head_span_ab.json): span 2 takes 16 % and 12 % off the scan launch of
 // span 1 on ring 1, and ring 2 x span 2 is within half a percent of ring 1 x span 2 at either size
@@ -117,17 +128,25 @@ struct ScanRun {
 //           here and is never used.  HIST mode keeps its HM_HIST_BINS bins at the same offset (they are only read by that
 //           request) and the slack's bytes behind them
 //   queue   16 bytes: the item queue's broadcast word
-template <int NG, int BF, int TM, int WPB, int SUB, int RING = 0, int SPAN_ASK = 1>
+// A ring cut for three blocks per CU (kScanRings::blocks = 3) has no slack: ring and queue word only.
+template <int NG, int BF, int TM, int WPB, int SUB, int RING_ASK = 0, int SPAN_ASK = 1>
 struct ScanGeom {
-    static_assert(RING >= 0 && RING < HM_SCAN_RINGS && (RING == 0 || BF != 0), "rings other than 0: bf16 form");
+    static_assert(RING_ASK >= 0 && RING_ASK < HM_SCAN_RINGS && (RING_ASK == 0 || BF != 0), "rings other than 0: bf16 form");
+    static constexpr int RS = hm_row_floats(NG);            // fp32 image: floats per row
+    static constexpr int RB16 = 16 * hm_row16_chunks(NG);   // bf16 image: bytes per row (NG chunks of 8 bf16 [+ the [x0 fp32] chunk])
+    static constexpr int ROW_BYTES = BF ? RB16 : RS * 4;
+    static constexpr int QUEUE_BYTES = 16;
+    // the ring of this instantiation: the one asked for, but ring 1 where a three-block ring was asked for with another span
+    // than 2 or at a width whose blocks, each rounded up to the allocation granule, do not fit a CU's LDS three at a time
+    static constexpr int ASK_BLOCKS = kScanRings[RING_ASK].blocks;
+    static constexpr int ASK_LDS = (kScanRings[RING_ASK].dist + 1) * 32 * kScanRings[RING_ASK].sub * ROW_BYTES + QUEUE_BYTES;
+    static constexpr int RING = (ASK_BLOCKS == 3 && !(SPAN_ASK == 2 && 3 * hm_lds_alloc(ASK_LDS) <= HM_LDS_PER_CU)) ? 1 : RING_ASK;
+    static constexpr int BLOCKS = kScanRings[RING].blocks ? kScanRings[RING].blocks : 2;   // resident blocks per CU the LDS map is cut for
     static constexpr int RSUB = kScanRings[RING].sub ? kScanRings[RING].sub : SUB;   // 32-column groups per ring slot
     static constexpr bool EXACT = kScanRings[RING].exact != 0;
     static constexpr int PLAN_COLS = 32 * SUB;              // partner rows per tile of the item plan
     static constexpr int COLS = 32 * RSUB;                  // partner rows per streamed tile
     static_assert(SUB % RSUB == 0, "an item's run of plan tiles is a whole number of ring tiles");
-    static constexpr int RS = hm_row_floats(NG);            // fp32 image: floats per row
-    static constexpr int RB16 = 16 * hm_row16_chunks(NG);   // bf16 image: bytes per row (NG chunks of 8 bf16 [+ the [x0 fp32] chunk])
-    static constexpr int ROW_BYTES = BF ? RB16 : RS * 4;
     static constexpr int TILE_BYTES = COLS * ROW_BYTES;
     static constexpr int NP = BF ? (NG + 1) / 2 : NG + 1;   // k-steps: fp32: NG spatial groups + time; bf16: two chunks per step
     static constexpr int NPIECE = TILE_BYTES / 1024;        // 1 KiB pieces per tile
@@ -142,8 +161,9 @@ struct ScanGeom {
     // tiles in flight ahead of the one being computed.  A ring other than 0 asks for its depth and gets what fits the
     // block's half of a CU's LDS beside the slack and the queue word (wide rows: 17 chunks keep 3 in flight where 13 keep 4)
     static constexpr int SLOTS_MAX = (HM_LDS_PER_BLOCK - 32 * ROW_BYTES - 16) / TILE_LDS;
+    // (a three-block ring exists only where its full depth fits: RING above)
     static constexpr int DIST = RING == 0 ? (BF ? HM_DIST_BF16 : 1)
-                                          : (kScanRings[RING].dist + 1 <= SLOTS_MAX ? kScanRings[RING].dist : (SLOTS_MAX > 2 ? SLOTS_MAX - 1 : 1));
+                                          : (BLOCKS == 3 || kScanRings[RING].dist + 1 <= SLOTS_MAX ? kScanRings[RING].dist : (SLOTS_MAX > 2 ? SLOTS_MAX - 1 : 1));
     static constexpr int NBUF = DIST + 1;                   // ring slots
     // slots computed per barrier (ScanRun): what was asked for where the ring has the slots for it (16 chunks keep 3 padded
     // slots: span 1), and 1 on ring 0
@@ -158,12 +178,14 @@ struct ScanGeom {
     static_assert(SPAN == 1 || ScanRun::outstanding_max(NBUF, SPAN) <= DIST - SPAN, "a span's waits leave less in flight than span 1's");
 
     static constexpr int RING_BYTES = NBUF * TILE_LDS;
-    static constexpr int SLACK_BYTES = 32 * ROW_BYTES;
+    static constexpr int SLACK_BYTES = BLOCKS == 3 ? 0 : 32 * ROW_BYTES;
     static constexpr int HIST_OFF = RING_BYTES;
-    static constexpr int QUEUE_BYTES = 16;
     HM_HOST_DEVICE_INLINE static constexpr int queue_off(int mode)
     {
         return RING_BYTES + SLACK_BYTES + (mode == HM_MODE_HIST ? 4 * HM_HIST_BINS : 0);
     }
     HM_HOST_DEVICE_INLINE static constexpr int lds_bytes(int mode) { return queue_off(mode) + QUEUE_BYTES; }
+    static_assert(BLOCKS != 3 || (EXACT && NBUF == 4 && SPAN == 2 && RING_BYTES + QUEUE_BYTES == 4 * TILE_BYTES + 16), "a three-block ring: four exact slots and the queue word");
+    static_assert(BLOCKS != 3 || 3 * hm_lds_alloc(RING_BYTES + QUEUE_BYTES) <= HM_LDS_PER_CU, "three blocks, each rounded up to the allocation granule, fit a CU's LDS");
+    static_assert(BLOCKS != 3 || ScanRun::outstanding_max(NBUF, SPAN) == 0, "a three-block ring: every tile wait is vmcnt(0)");
 };

@@ -826,8 +826,9 @@ int hm_debug_force_cut(hm_engine* e, uint32_t cut_bits, int64_t k, float c);
  * that draws its items from a device counter) and "dyn_slots" (size of that resident grid; 0 = what the device holds), "head" (k-steps of the argmin scan's
  * head test: the value the library was built with, 3, or 0 for the kernels without the test; the library launches the head kernels
  * only where it expects a tight bound -- from the third merge into a table on), "head_force" (1: on every eligible launch), "head_ring" (the head kernels' partner-tile
- * ring: 1 (default) = 64-column padded slots, three in flight; 2 = 64-column slots of the tile's own size, four in flight; 0 = the 128-column
- * ring of every other kernel), "head_span" (ring slots a head kernel computes between two barriers: 2 (default) = 128 columns as one
+ * ring: 1 = 64-column padded slots, three in flight; 2 = 64-column slots of the tile's own size, four in flight; 0 = the 128-column
+ * ring of every other kernel), "head_blocks" (3 (default) = the head kernels' ring 3: four 64-column slots of the tile's own size and nothing
+ * behind them, three blocks per CU and three waves per SIMD -- span 2 at 8 and 13 chunks, ring 1 otherwise; 2 = ring 1), "head_span" (ring slots a head kernel computes between two barriers: 2 (default) = 128 columns as one
  * pipeline with a straight-line body for the tiles right of the block's rows, or 1; rings 1 and 2 only, and span 1 where a width's ring has fewer
  * than four slots), "pipeline" (0: the standard loop
  * strictly sequential), "pipeline_pairs", "pipe_fault_at", "exact_search" (1: every top-k / count through the prefilter-free
