@@ -33,71 +33,18 @@ from __future__ import annotations
 import json
 import logging
 import os
-import time
 from typing import Dict, List, Optional, Tuple
 
-import numpy as np
 import torch
 from tqdm import tqdm
 
-from .greedy_matcher import make_matcher
 from .hyperbolic_merge import TQDM_OFF, HyperbolicTokenizer, _loop_without_cyclic_gc
+from .scoring import CompressionTerm, now_ms, select_row_major  # noqa: F401  (select_row_major: imported from here by callers)
 
 logger = logging.getLogger(__name__)
 
-ROW_MAJOR_FIT = 1 << 16      # candidate totals up to this size are listed in one call
 
-
-def _best_of(i: np.ndarray, j: np.ndarray, d: np.ndarray) -> Optional[Tuple[int, int, float]]:
-    """Smallest (d, i, j) of a candidate list, or None."""
-    if len(i) == 0:
-        return None
-    t = np.lexsort((j, i, d))[0]
-    return int(i[t]), int(j[t]), float(d[t])
-
-
-def select_row_major(eng, c: float, thr: float, k: int, fit: int = ROW_MAJOR_FIT):
-    """The first ``k`` candidates ``(i, j, d)`` in row-major order and the best ``(i, j, d)`` of the remaining ones by
-    smallest d, then row-major (None when there is no remainder).  No candidates at all: ``([], None)``.
-
-    Built only from ``eng.topk(..., k=0, count=True)`` row-range counts, ``eng.candidates(row_begin, row_end)`` and
-    ``eng.argmin(row_begin, ...)``: when the total fits, one listing is sliced; otherwise the smallest ``r`` whose
-    rows ``[0, r)`` hold at least ``k`` candidates is found (galloping, then bisection), rows ``[0, r)`` are listed,
-    and the remainder's best is the better of that listing's leftover and ``argmin`` over rows ``[r, n)``."""
-    k = max(int(k), 0)
-    total = eng.topk(c, thr, 0, 0, -1, count=True)[3]
-    if total == 0:
-        return [], None
-    if total <= max(k, fit):
-        i, j, d, _ = eng.candidates(c, thr)
-        first = list(zip(i[:k].tolist(), j[:k].tolist(), [float(x) for x in d[:k].tolist()]))
-        return first, _best_of(i[k:], j[k:], d[k:])
-    n = eng.n
-
-    def count_rows(r: int) -> int:
-        return eng.topk(c, thr, 0, 0, r, count=True)[3]
-
-    lo, hi = 0, 1                          # count_rows(lo) < k (rows [0, 0) hold nothing)
-    while hi < n and count_rows(hi) < k:
-        lo, hi = hi, min(2 * hi, n)
-    while hi - lo > 1:
-        mid = (lo + hi) // 2
-        if count_rows(mid) >= k:
-            hi = mid
-        else:
-            lo = mid
-    i, j, d, _ = eng.candidates(c, thr, 0, hi)
-    first = list(zip(i[:k].tolist(), j[:k].tolist(), [float(x) for x in d[:k].tolist()]))
-    best = _best_of(i[k:], j[k:], d[k:])
-    hit = eng.argmin(c, thr, hi, n) if hi < n else None
-    if hit is not None:
-        cand = (hit[1], hit[2], float(hit[0]))
-        if best is None or (cand[2], cand[0], cand[1]) < (best[2], best[0], best[1]):
-            best = cand
-    return first, best
-
-
-class CompressionAwareTokenizer(HyperbolicTokenizer):
+class CompressionAwareTokenizer(CompressionTerm, HyperbolicTokenizer):
     """Merges chosen by a mix of compression ratio on a corpus sample and hyperbolic distance."""
 
     def __init__(
@@ -133,34 +80,10 @@ class CompressionAwareTokenizer(HyperbolicTokenizer):
         self.sample_size = sample_size
         self.corpus_sample = corpus_sample or []
         self.tokenize_cache: Dict[str, int] = {}
-        self._matcher = None
-        self._corpus_state = None      # (corpus copy, key -> representative index, representatives, multiplicities)
         self.last_timing = {}          # ms of the last _best_scored: select / matcher_device / matcher_call / score
 
     # ------------------------------------------------------------------------------------------
-    # greedy longest match (reference :91-120)
-    # ------------------------------------------------------------------------------------------
-    def _tokenize_with_vocab(self, text: str, vocab: List[str]) -> List[str]:
-        """Greedy longest match over ``vocab``, single characters where nothing matches.  The longest matching
-        entry is found by length instead of by scanning a sorted copy of the vocabulary at every position: two
-        matching entries of the same length are the same string, so the tokens are the reference's.  Empty entries
-        never match."""
-        entries = set(vocab)
-        entries.discard("")
-        longest = max((len(t) for t in entries), default=1)
-        out, k = [], 0
-        while k < len(text):
-            piece = text[k]
-            for width in range(min(longest, len(text) - k), 1, -1):
-                if text[k:k + width] in entries:
-                    piece = text[k:k + width]
-                    break
-            out.append(piece)
-            k += len(piece)
-        return out
-
-    # ------------------------------------------------------------------------------------------
-    # compression-aware scoring (reference :122-190)
+    # compression-aware scoring (reference :122-190; the greedy longest match :91-120 and its counts: CompressionTerm)
     # ------------------------------------------------------------------------------------------
     def _original_tokens(self) -> int:
         """``tokenize_cache["original"]``: computed at the first scoring that has candidates, never refreshed."""
@@ -172,61 +95,15 @@ class CompressionAwareTokenizer(HyperbolicTokenizer):
                 cache["original"] = sum(len(self.tokenize(text)) for text in self.corpus_sample)
         return cache["original"]
 
-    def _corpus(self):
-        """Representative lines: the first text of every cache key ``text[:20]`` (a later text with the same key
-        reuses the first one's count, reference :155-159), with the number of texts that share the key."""
-        st = self._corpus_state
-        if st is None or st[0] != list(self.corpus_sample):
-            index, reps, mult = {}, [], []
-            for text in self.corpus_sample:
-                key = text[:20]
-                r = index.get(key)
-                if r is None:
-                    index[key] = len(reps)
-                    reps.append(text)
-                    mult.append(1)
-                else:
-                    mult[r] += 1
-            st = (list(self.corpus_sample), index, reps, np.array(mult, np.int64))
-            self._corpus_state = st
-            if self._matcher is not None:
-                self._matcher.set_corpus(reps, st[3])
-        return st
-
-    def _greedy_counts(self, pairs: List[Tuple[int, int]], per_line: bool):
-        """Counts of the representative lines under vocabulary + vocab[i] + vocab[j] for every pair."""
-        _, _, reps, mult = self._corpus()
-        if self._matcher is None:
-            self._matcher = make_matcher(self.device)
-            self._matcher.set_corpus(reps, mult)
-        self._matcher.sync(self.vocab)
-        vocab = self.vocab
-        return self._matcher.count([vocab[i] + vocab[j] for i, j in pairs], per_line=per_line)
-
     def _merged_totals(self, pairs: List[Tuple[int, int]], materialise: bool) -> List[int]:
         """``merged_tokens`` of every pair (reference :152-161), cache entries honoured.  ``materialise``: leave every
         ``merge_{i}_{j}_{text[:20]}`` entry in ``tokenize_cache`` as the reference does."""
-        cache = self.tokenize_cache
         if not pairs:
             return []
-        if not materialise and not any(key.startswith("merge_") for key in cache):
+        if not materialise and not any(key.startswith("merge_") for key in self.tokenize_cache):
             totals, _ = self._greedy_counts(pairs, per_line=False)
             return [int(t) for t in totals.tolist()]
-        _, index, _, _ = self._corpus()
-        totals, counts = self._greedy_counts(pairs, per_line=True)
-        keys = [text[:20] for text in self.corpus_sample]
-        rows = [index[key] for key in keys]
-        out = []
-        for c, (i, j) in enumerate(pairs):
-            line = counts[c].tolist()
-            merged = 0
-            for key, r in zip(keys, rows):
-                name = f"merge_{i}_{j}_{key}"
-                if name not in cache:
-                    cache[name] = line[r]
-                merged += cache[name]
-            out.append(merged)
-        return out
+        return self._cached_merge_counts(pairs)
 
     def _scores(self, evaluated: List[Tuple[int, int, float]], materialise: bool) -> List[float]:
         original = self._original_tokens()
@@ -270,17 +147,17 @@ class CompressionAwareTokenizer(HyperbolicTokenizer):
                 return None
             d, i, j = hit
             return i, j, 1.0 / (1.0 + d)
-        t0 = _now()
+        t0 = now_ms()
         first, rest = select_row_major(eng, self.curvature, thr, self.sample_size)
-        timing["select_ms"] = _now() - t0
+        timing["select_ms"] = now_ms() - t0
         if not first and rest is None:
             self.last_timing = timing
             return None
         best = None
         if first:
-            t1 = _now()
+            t1 = now_ms()
             scores = self._scores(first, materialise=False)
-            timing["matcher_call_ms"] = _now() - t1
+            timing["matcher_call_ms"] = now_ms() - t1
             timing["matcher_device_ms"] = float(getattr(self._matcher, "last_device_ms", 0.0))
             t = max(range(len(scores)), key=scores.__getitem__)       # first maximum: the stable sort's pick
             best = (first[t][0], first[t][1], scores[t])
@@ -356,6 +233,3 @@ class CompressionAwareTokenizer(HyperbolicTokenizer):
         tok.sample_size = compression_config.get("sample_size", 100)
         return tok
 
-
-def _now() -> float:
-    return time.perf_counter() * 1e3

@@ -20,10 +20,15 @@ What runs where
   (``:266-289``): the adjacent-pair histogram of the tokenised corpus, in the dict's insertion order (pair_counter.py).
 * **GPU (``hm_greedy_count``)** -- the greedy longest-match counts behind the compression term (``:813-899``): all
   cache entries a batch of candidates is missing, in one call (``greedy_matcher.GreedyMatcher``).
+* **GPU (``hm_ngram_count``)** -- the 2..5-gram histogram of ``_compute_corpus_statistics`` (``:388-437``) and the
+  "substring of at least 5 common words" rule of ``_is_potential_morpheme`` (``:439-483``), ngram_counter.py.
 * **host Python, reference order kept** -- everything that consumes an RNG or touches strings:
   ``torch.randperm`` per candidate (same call order, so the same samples), the frequency table,
   compression and morphology heuristics, phase logic, threshold dynamics, statistics sampling with
   ``random.sample``, the sort by combined score (Python's stable ``list.sort`` on the same keys).
+
+The frequency + coherence, morphology and compression terms are the mixins of scoring.py, shared with the three
+stand-alone classes; this class switches each off with its ``use_*`` flag.
 
 Adaptive curvature: the reference's step raises at ``loss.backward()`` (``:774``; ``distance``
 re-wraps ``c`` with ``torch.tensor`` and detaches it, F8), so there is nothing to be identical to.
@@ -39,9 +44,6 @@ from __future__ import annotations
 import json
 import logging
 import os
-import random
-import re
-from collections import Counter
 from dataclasses import dataclass
 from typing import Any, Dict, List, Optional, Set, Tuple, Union
 
@@ -49,9 +51,10 @@ import numpy as np
 import torch
 from tqdm import tqdm
 
-from .fast_hyperbolic_merge import CandidateList, FastHyperbolicTokenizer, MergeCandidate
+from .fast_hyperbolic_merge import CandidateList, FastHyperbolicTokenizer, MergeCandidate, _sample_pairs
 from .hyperbolic_merge import TQDM_OFF, _loop_without_cyclic_gc
-from .pair_counter import count_lines_device, read_corpus_lines, tokenize_customised
+from .scoring import (COHERENCE_SAMPLES, PREFIXES, SUFFIXES, CompressionTerm, FrequencyTerm,  # noqa: F401
+                      MorphologyTerm, _row_means, coherence_batch, randperm_prefixes, read_frequencies, write_frequencies)
 
 try:  # the reference consults WordNet when nltk is installed (:39-47); it is optional here too
     import nltk  # noqa: F401
@@ -64,9 +67,6 @@ except ImportError:
 logger = logging.getLogger(__name__)
 
 PHASE_THRESHOLDS = {1: 0.05, 2: 0.1}          # reference :525-530; any later phase: 0.2
-PREFIXES = {"re", "un", "in", "im", "il", "ir", "dis", "en", "em", "non", "de", "pre", "pro", "mis"}
-SUFFIXES = {"ing", "ed", "er", "est", "ly", "ity", "ment", "ness", "able", "ible", "al", "ial"}
-COHERENCE_SAMPLES = 50                        # reference :324
 
 
 @dataclass
@@ -83,128 +83,13 @@ class EnhancedMergeCandidate(MergeCandidate):
         return self.combined_score < other.combined_score
 
 
-_RANDPERM_HELPER_OK = None
-
-
-def _randperm_helper_ok() -> bool:
-    """One-time check of the library's MT19937 helper against THIS torch build's ``torch.randperm`` -- prefix values and
-    the generator state left behind, at a small n and at n = 100 003 (the helper follows randperm's 32-bit draw and
-    Fisher-Yates order; a build that changes either would otherwise sample other coherence rows than the reference).
-    On a mismatch the helper is not used again: plain ``torch.randperm`` calls."""
-    global _RANDPERM_HELPER_OK
-    if _RANDPERM_HELPER_OK is None:
-        _RANDPERM_HELPER_OK = True                    # (so that the calls below go through the helper)
-        keep = torch.get_rng_state()
-        ok = True
-        try:
-            for n, ns, count in ((37, 5, 3), (100003, COHERENCE_SAMPLES, 2)):
-                torch.manual_seed(1234567 + n)
-                want = np.stack([torch.randperm(n)[:ns].numpy() for _ in range(count)]).astype(np.int32)
-                st_want = torch.get_rng_state()
-                torch.manual_seed(1234567 + n)
-                got = randperm_prefixes(n, ns, count)
-                ok = ok and np.array_equal(got, want) and torch.equal(torch.get_rng_state(), st_want)
-        except Exception:
-            ok = False
-        finally:
-            torch.set_rng_state(keep)
-        _RANDPERM_HELPER_OK = bool(ok)
-        if not ok:
-            logger.warning("hm_randperm_prefix disagrees with this torch build's randperm: using torch.randperm")
-    return _RANDPERM_HELPER_OK
-
-
-def randperm_prefixes(n: int, ns: int, count: int) -> np.ndarray:
-    """``[torch.randperm(n)[:ns] for _ in range(count)]`` as an int32 ``[count, ns]`` array, consuming torch's
-    CPU generator exactly as those calls do.  Served by the library's host helper ``hm_randperm_prefix`` (the
-    generator's MT19937 state is read from and written back to ``torch.get/set_rng_state``); plain
-    ``torch.randperm`` calls when that is not possible (n >= 2^32 / 20, an unexpected state layout)."""
-    out = np.empty((count, ns), np.int32)
-    if count == 0 or ns == 0:
-        for _ in range(count):
-            torch.randperm(n)
-        return out
-    st = torch.get_rng_state()
-    if st.numel() == 5056 and n < (2 ** 32 - 1) // 20 and ns <= 4096 and _randperm_helper_ok():
-        from .. import _lib
-        import ctypes as C
-        raw = st.numpy().copy()
-        # CPUGeneratorImplStateLegacy: u64 seed | i32 left | i32 seeded | u64 next | u64 state[624] | ...
-        left = raw[8:12].view(np.int32)
-        seeded = raw[12:16].view(np.int32)
-        nxt = raw[16:24].view(np.uint64)
-        words = raw[24:24 + 624 * 8].view(np.uint64)
-        if seeded[0] == 1 and 1 <= left[0] <= 624:
-            mt = words.astype(np.uint32)
-            c_left, c_next = C.c_int32(int(left[0])), C.c_uint32(int(nxt[0]))
-            rc = _lib.load().hm_randperm_prefix(C.c_void_p(mt.ctypes.data), C.byref(c_left), C.byref(c_next), int(n), int(ns),
-                                                int(count), C.c_void_p(out.ctypes.data))
-            if rc == 0:
-                words[:] = mt
-                left[0] = c_left.value
-                nxt[0] = c_next.value
-                torch.set_rng_state(torch.from_numpy(raw))
-                return out
-    for t in range(count):
-        out[t] = torch.randperm(n)[:ns].numpy()
-    return out
-
-
-def _row_means(dist: np.ndarray, keep: np.ndarray) -> np.ndarray:
-    """``np.mean`` of the kept entries of every row in float64 -- the value ``np.mean(list_of_floats)``
-    gives the reference (``:340``), same summation order: full rows go through one reduction over the
-    contiguous axis (numpy's pairwise sum, as for a 1-D array); rows with skipped samples one by one."""
-    d64 = dist.astype(np.float64)
-    out = np.empty(d64.shape[0], np.float64)
-    full = keep.all(axis=1)
-    if full.any():
-        out[full] = np.add.reduce(np.ascontiguousarray(d64[full]), axis=1) / d64.shape[1]
-    for r in np.nonzero(~full)[0].tolist():
-        vals = d64[r][keep[r]]
-        out[r] = np.mean(vals) if vals.size else np.nan       # empty: the caller returns 0.0 (:335-336)
-    return out
-
-
-def coherence_batch(eng, ii: np.ndarray, jj: np.ndarray, w: np.ndarray, draw, c: float, merge_threshold: float,
-                    shard=None) -> np.ndarray:
-    """``1 / (1 + exp(mean distance - merge_threshold))`` of every candidate's simulated merged embedding
-    ``exp_map(x_i, w * log_map(x_i, x_j))`` to its sampled rows, 0.0 when no sample is kept (the reference's
-    ``_compute_semantic_coherence`` of the enhanced class ``:291-346`` and of FrequencyAwareHyperbolicTokenizer
-    ``:114-166``, which are the same arithmetic).  ``draw(k)`` returns the next ``k`` candidates' samples (one
-    ``torch.randperm(n)[:50]`` each): the RNG calls happen in list order; midpoints and all ``count x 50`` distances
-    are ONE kernel launch (two when the list is long: the second half's samples are drawn while the first half runs);
-    mean / sigmoid in float64 as ``np.mean`` / ``np.exp`` give them."""
-    count = len(ii)
-    if count == 0:
-        return np.zeros(0, np.float64)
-    if shard is not None:
-        from ..sharding import sharded_coherence
-        samples = draw(count)          # (every rank draws the same samples: same seeded generator)
-        dist = sharded_coherence(eng, shard, ii, jj, w.astype(np.float32), samples, c)
-    elif count >= 64 and hasattr(eng, "coherence_distances_begin"):
-        # two halves, samples drawn in candidate order as ever: while the first half's kernel and result copy run, the
-        # host draws the second half's permutations (the long pole: one MT19937 pass over n draws per candidate)
-        h = count // 2
-        s0 = draw(h)
-        pend = eng.coherence_distances_begin(ii[:h], jj[:h], w[:h].astype(np.float32), s0, c)
-        s1 = draw(count - h)
-        d1 = eng.coherence_distances(ii[h:], jj[h:], w[h:].astype(np.float32), s1, c)
-        samples = np.concatenate([s0, s1])
-        dist = np.concatenate([eng.coherence_distances_end(pend), d1])
-    else:
-        samples = draw(count)
-        dist = eng.coherence_distances(ii, jj, w.astype(np.float32), samples, c)
-    keep = (samples != ii[:, None]) & (samples != jj[:, None])
-    avg = _row_means(dist, keep)
-    with np.errstate(over="ignore", invalid="ignore"):
-        coh = 1.0 / (1.0 + np.exp(avg - merge_threshold))
-    coh[~keep.any(axis=1)] = 0.0
-    return coh
-
-
-class EnhancedFastHyperbolicTokenizer(FastHyperbolicTokenizer):
+class EnhancedFastHyperbolicTokenizer(FrequencyTerm, MorphologyTerm, CompressionTerm, FastHyperbolicTokenizer):
     """``FastHyperbolicTokenizer`` + frequency / coherence / compression / morphology scoring,
-    hierarchical phases and adaptive curvature."""
+    hierarchical phases and adaptive curvature.  The three terms are the mixins of scoring.py, each behind its
+    ``use_*`` flag; the WordNet branch of the predicates is taken when nltk is installed."""
+
+    _logger = logger
+    _wordnet = wordnet
 
     def __init__(
         self,
@@ -308,116 +193,14 @@ class EnhancedFastHyperbolicTokenizer(FastHyperbolicTokenizer):
         return float(c.detach()) if isinstance(c, torch.Tensor) else float(c)
 
     # ------------------------------------------------------------------------------------------
-    # frequency-aware scoring
+    # frequency-aware scoring (reference :266-372: FrequencyTerm)
     # ------------------------------------------------------------------------------------------
-    def _compute_pair_frequencies(self, corpus_path: str) -> None:
-        """Adjacent-token pair counts over a corpus file (reference ``:266-289``)."""
-        if not self.use_frequency_aware:
-            return
-        logger.info("Computing pair frequencies from corpus...")
-        if self.device.type == "cuda" and not tokenize_customised(self):
-            # hm_tokenize_batch + hm_pairfreq_add over slabs of lines: the same dict, in the same order (pair_counter.py)
-            seen = count_lines_device(self, read_corpus_lines(corpus_path), self.pair_frequencies)
-        else:
-            seen = 0
-            with open(corpus_path, "r", encoding="utf-8") as f:
-                for line in tqdm(f, desc="Computing frequencies", disable=TQDM_OFF):
-                    toks = self.tokenize(line.strip())
-                    for pair in zip(toks, toks[1:]):
-                        self.pair_frequencies[pair] = self.pair_frequencies.get(pair, 0) + 1
-                        seen += 1
-        logger.info(f"Computed frequencies for {len(self.pair_frequencies)} unique token pairs "
-                    f"from {seen} total pairs")
-
-    def _frequency_scores(self, ii: np.ndarray, jj: np.ndarray) -> np.ndarray:
-        """``log1p(freq(ti, tj)) / log1p(max freq)`` per candidate (reference ``:348-372``)."""
-        out = np.zeros(len(ii), np.float64)
-        if not self.use_frequency_aware or not self.pair_frequencies:
-            return out
-        pf = self.pair_frequencies
-        # max over the table (the reference recomputes it for every candidate, :368): once per table state here --
-        # re-derived whenever the dict object or its size changes and at the start of every optimize_merges call
-        key = (id(pf), len(pf))
-        cached = getattr(self, "_freq_top", None)
-        if cached is None or cached[0] != key:
-            cached = (key, max(pf.values()))
-            self._freq_top = cached
-        top = cached[1]
-        if not top > 0:
-            return out
-        counts = np.fromiter((pf.get((self.vocab[a], self.vocab[b]), 0) for a, b in zip(ii.tolist(), jj.tolist())),
-                             dtype=np.float64, count=len(ii))
-        return np.log1p(counts) / np.log1p(top)
-
     def _compute_frequency_score(self, i: int, j: int) -> float:
         return float(self._frequency_scores(np.array([i]), np.array([j]))[0])
 
-    def _coherence_samples(self, count: int) -> np.ndarray:
-        """``torch.randperm(n)[:50]`` once per candidate, in candidate order (reference ``:324-325``:
-        the torch CPU generator is consumed exactly as there)."""
-        n = self.current_vocab_size
-        return randperm_prefixes(n, min(COHERENCE_SAMPLES, n), count)
-
-    def _semantic_coherence_batch(self, ii: np.ndarray, jj: np.ndarray) -> np.ndarray:
-        """Reference ``_compute_semantic_coherence`` (``:291-346``) for a list of candidates (``coherence_batch``)."""
-        count = len(ii)
-        if not self.use_frequency_aware or count == 0:
-            return np.zeros(count, np.float64)
-        lens = self._token_lengths()                      # len(vocab[r]), kept as an array and extended as tokens are appended
-        li, lj = lens[ii], lens[jj]
-        w = (lj / (li + lj)).astype(np.float64)           # weight_j, a Python double in the reference (:316)
-        return coherence_batch(self._get_engine(), ii, jj, w, self._coherence_samples, self._c(), self.merge_threshold,
-                               self.shard)
-
-    def _compute_semantic_coherence(self, i: int, j: int) -> float:
-        return float(self._semantic_coherence_batch(np.array([i], np.int32), np.array([j], np.int32))[0])
-
     # ------------------------------------------------------------------------------------------
-    # hierarchical strategy (host string logic, reference :388-633)
+    # hierarchical strategy (reference :388-633; the corpus statistics and the predicates :388-512: MorphologyTerm)
     # ------------------------------------------------------------------------------------------
-    def _compute_corpus_statistics(self, corpus_path: str) -> None:
-        """Word counts, 2..5-gram counts, and the frequent ones of each (reference ``:388-437``)."""
-        if not self.use_hierarchical:
-            return
-        logger.info("Computing corpus statistics for hierarchical merging...")
-        words, grams = Counter(), Counter()
-        with open(corpus_path, "r", encoding="utf-8") as f:
-            for line in tqdm(f, desc="Analyzing corpus", disable=TQDM_OFF):
-                found = re.findall(r"\b\w+\b", line.lower())
-                words.update(found)
-                for word in found:
-                    for n in range(2, min(6, len(word) + 1)):
-                        grams.update(word[k:k + n] for k in range(len(word) - n + 1))
-        self.token_frequencies = dict(words)
-        gram_cut = np.percentile(list(grams.values()), 80)
-        self.common_morphemes = {g for g, cnt in grams.items() if cnt >= gram_cut}
-        word_cut = np.percentile(list(words.values()), 70)
-        self.common_words = {w for w, cnt in words.items() if cnt >= word_cut}
-        logger.info(f"Identified {len(self.common_morphemes)} common morphemes and "
-                    f"{len(self.common_words)} common words")
-
-    def _is_potential_morpheme(self, token: str) -> bool:
-        """Reference ``:439-483``."""
-        if not self.use_hierarchical or token in self.common_morphemes:
-            return True
-        if NLTK_AVAILABLE:
-            if token in PREFIXES or token in SUFFIXES:
-                return True
-            if len(token) > 2 and any(wordnet.synsets(token, pos=p)
-                                      for p in (wordnet.NOUN, wordnet.VERB, wordnet.ADJ, wordnet.ADV)):
-                return True
-        if 2 <= len(token) <= 5 and sum(1 for w in self.common_words if token in w) >= 5:
-            return True
-        return False
-
-    def _is_valid_word(self, token: str) -> bool:
-        """Reference ``:485-512``."""
-        if not self.use_hierarchical or token in self.common_words:
-            return True
-        if NLTK_AVAILABLE and wordnet.synsets(token):
-            return True
-        return len(token) >= 3 and re.search(r"[aeiou]", token) is not None
-
     def _get_merge_phase_threshold(self) -> float:
         if not self.use_hierarchical:
             return self.merge_threshold
@@ -448,38 +231,23 @@ class EnhancedFastHyperbolicTokenizer(FastHyperbolicTokenizer):
         return out
 
     # ------------------------------------------------------------------------------------------
-    # compression-aware scoring (host string logic, reference :813-899)
+    # compression-aware scoring (reference :813-899; greedy tokenisation, matcher and cache entries: CompressionTerm)
     # ------------------------------------------------------------------------------------------
-    def _tokenize_with_vocab(self, text: str, vocab: List[str]) -> List[str]:
-        """Greedy longest match over ``vocab``, single characters where nothing matches (reference
-        ``:813-847``; the longest matching entry is found by length instead of by scanning a sorted
-        copy of the vocabulary at every position -- same tokens)."""
-        if not self.use_compression_aware:
-            return self.tokenize(text)
-        entries = set(vocab)
-        longest = max((len(t) for t in entries), default=1)
-        out, k = [], 0
-        while k < len(text):
-            for width in range(min(longest, len(text) - k), 0, -1):
-                piece = text[k:k + width]
-                if piece in entries:
-                    break
-            else:
-                piece = text[k]
-            if not piece:
-                piece = text[k]
-            out.append(piece)
-            k += len(piece)
-        return out
+    def _compression_texts(self) -> List[str]:
+        return self.corpus_sample[:10]           # the score reads the first ten texts and rescales (:872-889)
+
+    def _original_tokens(self) -> int:
+        cache = self.tokenize_cache
+        if "original" not in cache:
+            cache["original"] = sum(len(self.tokenize(text)) for text in self.corpus_sample)
+        return cache["original"]
 
     def _compute_compression_score(self, i: int, j: int) -> float:
         """Reference ``:849-899`` including its cache keys (``"original"``, ``merge_{i}_{j}_{text[:20]}``)."""
         if not self.use_compression_aware or not self.corpus_sample:
             return 0.0
         cache = self.tokenize_cache
-        if "original" not in cache:
-            cache["original"] = sum(len(self.tokenize(text)) for text in self.corpus_sample)
-        before = cache["original"]
+        before = self._original_tokens()
         trial_vocab = None
         after = 0
         used = min(len(self.corpus_sample), 10)
@@ -507,34 +275,12 @@ class EnhancedFastHyperbolicTokenizer(FastHyperbolicTokenizer):
                 or cls._tokenize_with_vocab is not own._tokenize_with_vocab
                 or {"_compute_compression_score", "_tokenize_with_vocab"} & set(self.__dict__)):
             return
+        self._original_tokens()
         cache = self.tokenize_cache
-        if "original" not in cache:
-            cache["original"] = sum(len(self.tokenize(text)) for text in self.corpus_sample)
         keys = [text[:20] for text in self.corpus_sample[:10]]
         missing = [(a, b) for a, b in pairs if any(f"merge_{a}_{b}_{k}" not in cache for k in keys)]
-        if not missing:
-            return
-        index, reps = {}, []
-        for text, key in zip(self.corpus_sample, keys):
-            if key not in index:
-                index[key] = len(reps)
-                reps.append(text)
-        state = getattr(self, "_greedy_state", None)
-        if state is None:
-            from .greedy_matcher import GreedyMatcher
-            state = self._greedy_state = [GreedyMatcher(self.device), None]
-        matcher = state[0]
-        if state[1] != reps:
-            matcher.set_corpus(reps)
-            state[1] = reps
-        matcher.sync(self.vocab)
-        vocab = self.vocab
-        _, counts = matcher.count([vocab[a] + vocab[b] for a, b in missing], per_line=True)
-        for (a, b), row in zip(missing, counts.tolist()):
-            for key in keys:
-                name = f"merge_{a}_{b}_{key}"
-                if name not in cache:
-                    cache[name] = row[index[key]]
+        if missing:
+            self._cached_merge_counts(missing)
 
     # ------------------------------------------------------------------------------------------
     # combined score
@@ -871,11 +617,7 @@ class EnhancedFastHyperbolicTokenizer(FastHyperbolicTokenizer):
         draw in the reference's order, the distances in one kernel call."""
         n = self.current_vocab_size
         draws = min(1000, n * (n - 1) // 2)
-        ii, jj = [], []
-        for _ in range(draws):
-            a, b = random.sample(range(n), 2)
-            ii.append(a)
-            jj.append(b)
+        ii, jj = _sample_pairs(n, draws)
         if not ii:
             return []
         return [float(v) for v in self._get_engine().pair_distance(ii, jj, self._c())]
@@ -921,8 +663,7 @@ class EnhancedFastHyperbolicTokenizer(FastHyperbolicTokenizer):
             with open(os.path.join(path, "training_stats.json"), "w") as f:
                 json.dump({str(k): v for k, v in self.training_stats.items()}, f, indent=2)
         if self.use_frequency_aware and getattr(self, "pair_frequencies", None):
-            with open(os.path.join(path, "frequencies.json"), "w") as f:
-                json.dump({f"{a}|{b}": v for (a, b), v in self.pair_frequencies.items()}, f)
+            write_frequencies(path, self.pair_frequencies)
         if self.use_hierarchical:
             with open(os.path.join(path, "hierarchical_data.json"), "w") as f:
                 json.dump({"language": getattr(self, "language", "english"),
@@ -974,8 +715,7 @@ class EnhancedFastHyperbolicTokenizer(FastHyperbolicTokenizer):
                 logger.warning("Could not load adaptive curvature data")
         if tok.use_frequency_aware:
             try:
-                with open(os.path.join(path, "frequencies.json"), "r") as f:
-                    tok.pair_frequencies = {tuple(k.split("|")): v for k, v in json.load(f).items()}
+                tok.pair_frequencies = read_frequencies(path)
             except FileNotFoundError:
                 logger.warning("Could not load frequency data")
         if tok.use_hierarchical:

@@ -412,17 +412,6 @@ class FastHyperbolicTokenizer(HyperbolicTokenizer):
         self._engine_key = self._table_key()
         return k
 
-    def _token_lengths(self) -> np.ndarray:
-        """len(vocab[r]) for every row, kept as an array and extended as tokens are appended"""
-        lens = getattr(self, "_lens", None)
-        n = len(self.vocab)
-        if lens is None or len(lens) > n:
-            lens = np.fromiter(map(len, self.vocab), np.int64, n)
-        elif len(lens) < n:
-            lens = np.concatenate([lens, np.fromiter(map(len, self.vocab[len(lens):]), np.int64, n - len(lens))])
-        self._lens = lens
-        return lens
-
     def _plan_merges(self, found: "CandidateList", steps_left: int) -> None:
         """Every merge up to the next refresh is known when a refresh returns (this
         step merges ``S[0]``, the following ones pop 100 cached entries each and merge the first of them,

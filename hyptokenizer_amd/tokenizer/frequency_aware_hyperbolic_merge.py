@@ -39,16 +39,16 @@ import numpy as np
 import torch
 from tqdm import tqdm
 
-from .compression_aware_tokenizer import select_row_major
-from .enhanced_fast_hyperbolic_merge import COHERENCE_SAMPLES, coherence_batch, randperm_prefixes
 from .hyperbolic_merge import TQDM_OFF, HyperbolicTokenizer, _loop_without_cyclic_gc
-from .pair_counter import count_pair_frequencies
+from .scoring import FrequencyTerm, now_ms, read_frequencies, select_row_major, write_frequencies
 
 logger = logging.getLogger(__name__)
 
 
-class FrequencyAwareHyperbolicTokenizer(HyperbolicTokenizer):
+class FrequencyAwareHyperbolicTokenizer(FrequencyTerm, HyperbolicTokenizer):
     """Merges chosen by a mix of hyperbolic distance, corpus pair frequency and semantic coherence."""
+
+    _logger = logger
 
     def __init__(
         self,
@@ -83,81 +83,19 @@ class FrequencyAwareHyperbolicTokenizer(HyperbolicTokenizer):
         self.beta = beta
         self.gamma = gamma
         self.pair_frequencies: Dict[Tuple[str, str], int] = {}
-        self._freq_top = None          # ((id, len) of the dict, max count)
-        self._log1p = {}               # count -> np.log1p(count), the reference's scalar call
         self.last_timing = {}          # ms of the last scoring: list / rng / coherence / score_sort
         if corpus_path:
             self._compute_pair_frequencies(corpus_path)
 
     # ------------------------------------------------------------------------------------------
-    # corpus pass (reference :92-112)
+    # scoring (reference :168-199; the corpus pass :92-112, the frequency and coherence terms :114-191: FrequencyTerm)
     # ------------------------------------------------------------------------------------------
-    def _compute_pair_frequencies(self, corpus_path: str) -> None:
-        logger.info("Computing pair frequencies from corpus...")
-        total_pairs = count_pair_frequencies(self, corpus_path, self.pair_frequencies)
-        self._freq_top = None
-        logger.info(f"Computed frequencies for {len(self.pair_frequencies)} unique token pairs "
-                    f"from {total_pairs} total pairs")
-
-    # ------------------------------------------------------------------------------------------
-    # scoring (reference :114-199)
-    # ------------------------------------------------------------------------------------------
-    def _max_freq(self):
-        """``max(values) if dict else 1`` (reference ``:190``, recomputed per candidate there): once per dict state."""
-        pf = self.pair_frequencies
-        key = (id(pf), len(pf))
-        cached = self._freq_top
-        if cached is None or cached[0] != key:
-            cached = (key, max(pf.values()) if pf else 1)
-            self._freq_top = cached
-        return cached[1]
-
-    def _frequency_scores(self, ii: np.ndarray, jj: np.ndarray) -> np.ndarray:
-        """``np.log1p(freq) / np.log1p(max_freq)`` per candidate, 0 when ``max_freq <= 0`` (reference ``:185-191``)."""
-        top = self._max_freq()
-        if not top > 0:
-            return np.zeros(len(ii), np.float64)
-        pf, vocab, memo = self.pair_frequencies, self.vocab, self._log1p
-        logs = []
-        for a, b in zip(ii.tolist(), jj.tolist()):
-            c = pf.get((vocab[a], vocab[b]), 0)
-            v = memo.get(c)
-            if v is None:
-                v = memo[c] = np.log1p(c)
-            logs.append(v)
-        return np.asarray(logs, np.float64) / np.log1p(top)
-
-    def _coherence_samples(self, count: int) -> np.ndarray:
-        """``torch.randperm(n)[:50]`` once per candidate, in candidate order (reference ``:144-145``)."""
-        n = self.current_vocab_size
-        t0 = time.perf_counter()
-        out = randperm_prefixes(n, min(COHERENCE_SAMPLES, n), count)
-        self.last_timing["rng_ms"] = self.last_timing.get("rng_ms", 0.0) + (time.perf_counter() - t0) * 1e3
-        return out
-
-    def _semantic_coherence_batch(self, ii: np.ndarray, jj: np.ndarray) -> np.ndarray:
-        """Reference ``_compute_semantic_coherence`` (``:114-166``) for a list of candidates: weight
-        ``len(tj) / (len(ti) + len(tj))``, the float curvature, one RNG draw per candidate in list order."""
-        ii = np.ascontiguousarray(ii, np.int32)
-        jj = np.ascontiguousarray(jj, np.int32)
-        if len(ii) == 0:
-            return np.zeros(0, np.float64)
-        vocab = self.vocab
-        li = np.fromiter((len(vocab[a]) for a in ii.tolist()), np.int64, len(ii))
-        lj = np.fromiter((len(vocab[b]) for b in jj.tolist()), np.int64, len(jj))
-        w = (lj / (li + lj)).astype(np.float64)
-        return coherence_batch(self._get_engine(), ii, jj, w, self._coherence_samples, float(self.curvature),
-                               self.merge_threshold)
-
-    def _compute_semantic_coherence(self, i: int, j: int) -> float:
-        return float(self._semantic_coherence_batch(np.array([i], np.int32), np.array([j], np.int32))[0])
-
     def _scores(self, ii: np.ndarray, jj: np.ndarray, dd: np.ndarray) -> np.ndarray:
         """``alpha * (1 / (1 + d)) + beta * freq + gamma * coherence`` in float64, left to right (reference ``:197``)."""
         freq = self._frequency_scores(ii, jj)
-        t0 = time.perf_counter()
+        t0 = now_ms()
         coh = self._semantic_coherence_batch(ii, jj)
-        self.last_timing["coherence_ms"] = self.last_timing.get("coherence_ms", 0.0) + (time.perf_counter() - t0) * 1e3
+        self.last_timing["coherence_ms"] = self.last_timing.get("coherence_ms", 0.0) + (now_ms() - t0)
         dist_score = 1.0 / (1.0 + np.asarray(dd, np.float64))
         with np.errstate(invalid="ignore", over="ignore"):
             return self.alpha * dist_score + self.beta * freq + self.gamma * coh
@@ -189,9 +127,9 @@ class FrequencyAwareHyperbolicTokenizer(HyperbolicTokenizer):
     def _find_merge_candidates(self) -> List[Tuple[int, int, float]]:
         """Unscored ``(i, j, d)`` (no frequencies, ``beta > 0``) or scored ``(i, j, -score)`` sorted ascending."""
         self.last_timing = {}
-        t0 = time.perf_counter()
+        t0 = now_ms()
         i, j, d = self._distance_candidates()
-        self.last_timing["list_ms"] = (time.perf_counter() - t0) * 1e3
+        self.last_timing["list_ms"] = now_ms() - t0
         if len(i) == 0:
             return []
         if self.beta > 0 and not self.pair_frequencies:
@@ -201,10 +139,10 @@ class FrequencyAwareHyperbolicTokenizer(HyperbolicTokenizer):
             i, j, d = i[keep], j[keep], d[keep]
         dd = [float(x) for x in d.tolist()]
         scores = self._scores(i, j, np.asarray(dd, np.float64))
-        t1 = time.perf_counter()
+        t1 = now_ms()
         scored = [(a, b, -s) for a, b, s in zip(i.tolist(), j.tolist(), scores.tolist())]
         scored.sort(key=lambda x: x[2])
-        self.last_timing["score_sort_ms"] = (time.perf_counter() - t1) * 1e3
+        self.last_timing["score_sort_ms"] = now_ms() - t1
         return scored
 
     def _step_pick(self) -> Tuple[int, Optional[Tuple[int, int, float]]]:
@@ -259,9 +197,9 @@ class FrequencyAwareHyperbolicTokenizer(HyperbolicTokenizer):
                 continue
             no_candidate_count = 0
             i, j, score = best
-            t0 = time.perf_counter()
+            t0 = now_ms()
             self._merge_tokens(i, j)
-            self.last_timing["merge_ms"] = (time.perf_counter() - t0) * 1e3
+            self.last_timing["merge_ms"] = now_ms() - t0
             if not bar.disable:
                 bar.set_postfix({"vocab_size": self.current_vocab_size, "score": f"{-score:.4f}",
                                  "threshold": f"{self.merge_threshold:.4f}",
@@ -277,9 +215,7 @@ class FrequencyAwareHyperbolicTokenizer(HyperbolicTokenizer):
     # ------------------------------------------------------------------------------------------
     def save(self, path: str) -> None:
         super().save(path)
-        frequencies_json = {f"{k[0]}|{k[1]}": v for k, v in self.pair_frequencies.items()}
-        with open(os.path.join(path, "frequencies.json"), "w") as f:
-            json.dump(frequencies_json, f)
+        write_frequencies(path, self.pair_frequencies)
         with open(os.path.join(path, "freq_hyperparams.json"), "w") as f:
             json.dump({"alpha": self.alpha, "beta": self.beta, "gamma": self.gamma}, f)
 
@@ -299,10 +235,7 @@ class FrequencyAwareHyperbolicTokenizer(HyperbolicTokenizer):
         except FileNotFoundError:
             logger.warning("Hyperparameters file not found, using defaults")
         try:
-            with open(os.path.join(path, "frequencies.json"), "r") as f:
-                frequencies_json = json.load(f)
-            tok.pair_frequencies = {tuple(k.split("|")): v for k, v in frequencies_json.items()}
-            tok._freq_top = None
+            tok.pair_frequencies = read_frequencies(path)
         except FileNotFoundError:
             logger.warning("Frequencies file not found")
         return tok

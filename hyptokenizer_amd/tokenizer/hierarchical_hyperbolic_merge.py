@@ -39,7 +39,6 @@ from __future__ import annotations
 import json
 import logging
 import os
-import re
 from typing import Dict, List, Optional, Set, Tuple
 
 import torch
@@ -48,21 +47,21 @@ from tqdm import tqdm
 from .class_minima import (N_CLASSES, P1_LE2, P1_LE3, P3_BOOSTED, P3_OTHER, ClassMinima, SplitIndex, lexmin,
                            make_backend)
 from .hyperbolic_merge import TQDM_OFF, HyperbolicTokenizer, _loop_without_cyclic_gc
-from .ngram_counter import corpus_statistics, frequent_substrings
+from .scoring import MorphologyTerm
 
 logger = logging.getLogger(__name__)
 
-NLTK_AVAILABLE = False             # the reference's branch without nltk is the one reproduced
-_VOWEL = re.compile(r"[aeiou]")
+NLTK_AVAILABLE = False             # the reference's branch without nltk is the one reproduced (MorphologyTerm._wordnet stays None)
 _LIST_METHODS = ("_find_merge_candidates", "_is_potential_morpheme", "_is_valid_word", "_filter_morphologically_valid",
                  "_filter_word_valid")
 
 
-class HierarchicalHyperbolicTokenizer(HyperbolicTokenizer):
+class HierarchicalHyperbolicTokenizer(MorphologyTerm, HyperbolicTokenizer):
     """Hyperbolic tokenizer whose merges run in three phases: characters, subwords (morphemes), words."""
 
     #: iterations of the three phases (the reference's ``range(2000)``, ``range(5000)``, ``range(10000)``)
     PHASE_STEPS = (2000, 5000, 10000)
+    _logger = logger
 
     def __init__(
         self,
@@ -95,48 +94,25 @@ class HierarchicalHyperbolicTokenizer(HyperbolicTokenizer):
         self.token_frequencies: Dict[str, int] = {}
         self.common_morphemes: Set[str] = set()
         self.common_words: Set[str] = set()
-        self._sets = None              # ((id, len) of both sets, frequent substrings, split index A, split index B)
         self._cm = None                # (key, ClassMinima)
         self._cm_backend = None        # (engine, backend)
         if corpus_path:
             self._compute_corpus_statistics(corpus_path)
 
     # ------------------------------------------------------------------------------------------
-    # corpus statistics (reference :110-156)
-    # ------------------------------------------------------------------------------------------
-    def _compute_corpus_statistics(self, corpus_path: str) -> None:
-        logger.info("Computing corpus statistics for hierarchical merging...")
-        word_counter, morphemes, words = corpus_statistics(corpus_path, self.device)
-        self.token_frequencies = dict(word_counter)
-        self.common_morphemes = morphemes
-        self.common_words = words
-        logger.info(f"Identified {len(self.common_morphemes)} common morphemes and "
-                    f"{len(self.common_words)} common words")
-
-    # ------------------------------------------------------------------------------------------
-    # string sets: cached on the identity and size of the two sets
+    # string sets (the corpus statistics :110-156 and the predicates :158-204, NLTK absent: MorphologyTerm)
     # ------------------------------------------------------------------------------------------
     def _string_sets(self):
-        key = (id(self.common_morphemes), len(self.common_morphemes), id(self.common_words), len(self.common_words))
-        if self._sets is None or self._sets[0] != key:
-            frequent = frequent_substrings(self.common_words, self.device)
-            self._sets = (key, frequent, SplitIndex(set(self.common_morphemes) | frequent), SplitIndex(self.common_words))
-        return self._sets
+        """(key, frequent substrings, split index A, split index B): the split indexes list the exception partners
+        of each new row (class_minima.py)."""
+        sets = super()._string_sets()
+        if len(sets) == 2:                 # rebuilt for other sets: the split indexes join the cached tuple
+            sets = self._sets = sets + (SplitIndex(set(self.common_morphemes) | sets[1]), SplitIndex(self.common_words))
+        return sets
 
     # ------------------------------------------------------------------------------------------
-    # predicates and filters, NLTK absent (reference :158-277)
+    # filters (reference :206-277)
     # ------------------------------------------------------------------------------------------
-    def _is_potential_morpheme(self, token: str) -> bool:
-        if token in self.common_morphemes:
-            return True
-        # len 2..5 and a substring of at least 5 common words: exactly the set of such n-grams of the common words
-        return 2 <= len(token) <= 5 and token in self._string_sets()[1]
-
-    def _is_valid_word(self, token: str) -> bool:
-        if token in self.common_words:
-            return True
-        return len(token) >= 3 and _VOWEL.search(token) is not None
-
     def _filter_morphologically_valid(self, candidates: List[Tuple[int, int, float]]) -> List[Tuple[int, int, float]]:
         out = []
         for i, j, dist in candidates:

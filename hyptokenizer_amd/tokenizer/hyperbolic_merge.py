@@ -259,6 +259,17 @@ class HyperbolicTokenizer:
         li, lj = len(self.vocab[i]), len(self.vocab[j])
         return lj / (li + lj)
 
+    def _token_lengths(self) -> np.ndarray:
+        """len(vocab[r]) for every row, kept as an array and extended as tokens are appended"""
+        lens = getattr(self, "_lens", None)
+        n = len(self.vocab)
+        if lens is None or len(lens) > n:
+            lens = np.fromiter(map(len, self.vocab), np.int64, n)
+        elif len(lens) < n:
+            lens = np.concatenate([lens, np.fromiter(map(len, self.vocab[len(lens):]), np.int64, n - len(lens))])
+        self._lens = lens
+        return lens
+
     def _append_token(self, i: int, j: int) -> None:
         """The host half of a merge (reference ``:343-355``): strings, index, history."""
         left, right = self.vocab[i], self.vocab[j]

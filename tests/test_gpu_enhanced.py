@@ -1,7 +1,13 @@
 """GPU: BASELINE config 5 (EnhancedFastHyperbolicTokenizer) through the HIP kernels -- hm_coherence_batch (fused
 midpoint + <= 50 gathered distances per candidate), hm_project_table (in-place re-projection + image refresh) --
 against the G5 goldens captured from the reference and, bit for bit, against the CPU oracle.
-The comparisons themselves live in tests/test_enhanced_golden.py (they run there on the oracle double)."""
+The comparisons themselves live in tests/test_enhanced_golden.py (they run there on the oracle double).
+The class's morphology and compression terms on a HIP device (hm_ngram, hm_greedy_count through tokenizer/scoring.py)
+against host restatements written here."""
+import random
+import re
+from collections import Counter
+
 import numpy as np
 import pytest
 import torch
@@ -131,3 +137,102 @@ def test_nan_curvature_is_carried_like_the_reference_carries_it(oracle):
     assert np.isnan(fh[:, 0]).all()                            # every time coordinate after the re-projection
     assert np.array_equal(np.isnan(fh), np.isnan(fo)) and np.array_equal(hip[2][~np.isnan(fh)], ora[2][~np.isnan(fo)])   # (NaN payloads aside)
     assert hip[3] == ora[3]
+
+
+# ----------------------------------------------------------------------------------------------
+# the morphology and compression terms on a HIP device
+# ----------------------------------------------------------------------------------------------
+def _enhanced_hip(vocab, **kw):
+    from hyptokenizer_amd.tokenizer.enhanced_fast_hyperbolic_merge import EnhancedFastHyperbolicTokenizer
+    opts = dict(use_frequency_aware=False, use_hierarchical=False, use_adaptive_curvature=False, use_compression_aware=False)
+    opts.update(kw)
+    X = lorentz_table(len(vocab), 8, seed=6, scale=0.1)
+    return EnhancedFastHyperbolicTokenizer(list(vocab), torch.nn.Parameter(X), merge_threshold=0.5, device=torch.device("cuda"),
+                                           max_vocab_size=len(vocab) + 16, sign_convention="lorentz", **opts)
+
+
+def _corpus_lines():
+    """~300 lines: an empty line, a 1-character word, words longer than 5, upper case, and a letter whose lower() is two
+    code points (U+0130)"""
+    rnd = random.Random(21)
+    syllables = ["an", "ber", "co", "dis", "ing", "le", "ment", "o", "re", "st", "tion", "un", "\u00e9t", "\u4e2d\u6587"]
+    words = ["".join(rnd.choice(syllables) for _ in range(rnd.randint(1, 4))) for _ in range(150)] + ["a", "I", "\u0130stanbul", "x"]
+    lines = []
+    for k in range(300):
+        picked = [rnd.choice(words) for _ in range(rnd.randint(1, 9))]
+        if k % 7 == 0:
+            picked = [w.upper() if t % 2 else w.capitalize() for t, w in enumerate(picked)]
+        lines.append((", " if k % 3 else " ").join(picked) + ("." if k % 5 == 0 else ""))
+    lines[17] = ""
+    lines[40] = "a"
+    lines[41] = "\u0130STANBUL \u0130 internationalisation"
+    return lines
+
+
+@pytest.fixture(scope="module")
+def corpus_tokenizer(tmp_path_factory):
+    path = tmp_path_factory.mktemp("enhanced_corpus") / "corpus.txt"
+    path.write_text("\n".join(_corpus_lines()) + "\n", encoding="utf-8")
+    return _enhanced_hip([chr(0x61 + k) for k in range(26)], use_hierarchical=True, corpus_path=str(path)), str(path)
+
+
+def test_corpus_statistics_on_hip_equal_the_reference_loop(corpus_tokenizer):
+    tok, path = corpus_tokenizer
+    words, grams = Counter(), Counter()
+    with open(path, "r", encoding="utf-8") as f:
+        for line in f:
+            found = re.findall(r"\b\w+\b", line.lower())
+            words.update(found)
+            for word in found:
+                for n in range(2, min(6, len(word) + 1)):
+                    for k in range(len(word) - n + 1):
+                        grams[word[k:k + n]] += 1
+    # (lower() turns U+0130 into "i" + U+0307, which is no word character: the word splits there)
+    assert len("\u0130".lower()) == 2 and "stanbul" in words and "a" in words and "internationalisation" in words
+    assert list(tok.token_frequencies.items()) == list(words.items())
+    gram_cut = np.percentile(list(grams.values()), 80)
+    assert tok.common_morphemes == {g for g, c in grams.items() if c >= gram_cut} and len(tok.common_morphemes) > 50
+    word_cut = np.percentile(list(words.values()), 70)
+    assert tok.common_words == {w for w, c in words.items() if c >= word_cut} and len(tok.common_words) > 30
+
+
+def test_potential_morpheme_on_hip_equals_the_scan_of_the_common_words(corpus_tokenizer):
+    tok, _ = corpus_tokenizer
+    tok._wordnet = None                                   # (with nltk installed the class also consults WordNet)
+    common = tok.common_words
+    some = sorted(common)[:50]
+    tokens = sorted({w[k:k + n] for w in some for n in range(2, 6) for k in range(len(w) - n + 1)})
+    want = [t in tok.common_morphemes or sum(t in w for w in common) >= 5 for t in tokens]
+    scan = [sum(t in w for w in common) >= 5 for t in tokens]
+    assert len(tokens) > 200 and any(scan) and not all(want)
+    assert [tok._is_potential_morpheme(t) for t in tokens] == want
+    keep = tok.common_morphemes
+    tok.common_morphemes = set()                          # the scan alone decides (and the string-set cache is re-keyed)
+    assert [tok._is_potential_morpheme(t) for t in tokens] == scan
+    tok.common_morphemes = keep
+
+
+def test_compression_prefill_leaves_the_host_loops_cache():
+    vocab = list("abcdefgh ") + ["ab", "cd", "abc", "ef", "gh", "h a", "de", "fgh"]
+    stem = "abcdefgh abcdefgh abcd"[:20]
+    rnd = random.Random(4)
+    texts = [stem + " ab", "cdab efgh", "", stem + "efgh", "h a h a b"]
+    texts += ["".join(rnd.choice("abcdefgh ") for _ in range(rnd.randint(5, 60))) for _ in range(9)]
+    assert len(texts) == 14 and texts[0][:20] == texts[3][:20]
+    t2i = {t: k for k, t in enumerate(vocab)}
+    pairs = [(t2i[a], t2i[b]) for a, b in [("ab", "cd"), ("e", "f"), ("abc", "de"), ("ab", "cd"), (" ", "a"), ("gh", " "),
+                                           ("h", " "), ("cd", "ef")]]
+    assert len(pairs) == 8 and len(set(pairs)) == 7
+    tok = _enhanced_hip(vocab, use_compression_aware=True, corpus_sample=list(texts))
+    twin = _enhanced_hip(vocab, use_compression_aware=True, corpus_sample=list(texts))
+    twin._tokenize_with_vocab = twin._tokenize_with_vocab          # an instance-level override: no prefill
+    twin._prefill_compression_cache(pairs)
+    assert twin.tokenize_cache == {}
+    tok._prefill_compression_cache(pairs)
+    filled = list(tok.tokenize_cache.items())
+    want_scores = [twin._compute_compression_score(a, b) for a, b in pairs]
+    assert filled == list(twin.tokenize_cache.items())
+    assert [k for k, _ in filled][0] == "original" and len(filled) == 1 + 7 * 9          # 10 texts, 9 distinct keys
+    assert [tok._compute_compression_score(a, b) for a, b in pairs] == want_scores       # (the rescale by 14 / 10 included)
+    assert list(tok.tokenize_cache.items()) == filled
+    assert any(s > 0 for s in want_scores)
